@@ -11,10 +11,14 @@ Usage: python bench.py [--gpus N --steps K --warmup W]; for N > 1 launch with
        `python bench.py --gpus N` with no WORLD_SIZE in the environment starts those N ranks itself: the parent
        (which makes no GPU call) runs torch.distributed.run as a child process and exits with its code (the
        reference's DDP entry does the same, ultralytics/engine/trainer.py:197-200, utils/dist.py:56-66).
-Rank 0 prints ONE compact JSON line (< 4 KB): the contract fields, `roofline` of the dominant HIP operator (measured
-live with HIP events inside the timed region), `path_roofline`, `cpu_baseline` (the oracle CPU model timed on the
-host cores, rank 0 at N = 1 only) and, at N = 1, `configs`: BASELINE configs[3] (n1280, bs 8) and configs[4] (m640
-bf16, bs 64), each timed in its own region of the same process (value, ms_per_step, roofline / path fractions).
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line. Rank 0 prints
+ONE compact JSON line (< 4 KB): the contract fields, `roofline` of the dominant HIP operator (measured live with HIP
+events inside the timed region) and `path_roofline`. With --full the same process goes on after the headline region:
+`nms_loaded` (HIP NMS at 1k / 10k / 30k candidates), `cpu_baseline` (the oracle CPU model timed on the host cores,
+rank 0 at N = 1 only) and, at N = 1, `configs`: BASELINE configs[3] (n1280, bs 8) and configs[4] (m640 bf16, bs 64),
+each timed in its own region (value, ms_per_step, roofline / path fractions); these are null / absent otherwise.
+--dump-outputs DIR writes what the last timed step returned (out, counts, index) and a seeded sample of the Detect
+output they were cut from (pred) as DIR/<name>.npy: the inputs are seeded, so two builds can be compared array by array.
 Every per-operator figure (hip_ops, backbone_hip_ops, the full cpu_baseline) goes to the --detail-json file, which
 scripts/roofline_from_csv.py checks against --ops-csv. Roofline fractions are quoted against the ceiling of the
 arithmetic each kernel issues (perf.py).
@@ -226,6 +230,25 @@ def nms_loaded(dev, B=32, A=34000, nc=10, reps=10):
     return res
 
 
+DUMP_SAMPLE = 1 << 21  # elements of one dumped array above which a fixed seeded sample of it is written instead
+
+
+def dump_outputs(outputs, out_dir):
+    """--dump-outputs: every array of ``outputs`` as ``out_dir/<name>.npy`` (float32; the integer counts / indices
+    as float64). An array of more than DUMP_SAMPLE elements is cut to that many flat positions drawn once from a
+    seed-0 generator (sorted, the same for every run of the same shape), so the directory stays far below 64 MB."""
+    import numpy as np
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, t in outputs.items():
+        t = t.detach().cpu().contiguous()
+        t = t.float() if t.is_floating_point() else t.double()
+        if t.numel() > DUMP_SAMPLE:
+            pos = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0))
+            t = t.reshape(-1)[pos.sort().values]
+        np.save(out_dir / f"{name}.npy", t.numpy())
+
+
 def load_traffic():
     p = ROOT / "profiles" / "traffic.json"
     if p.exists():
@@ -236,9 +259,11 @@ def load_traffic():
     return None
 
 
-def measure(name, world, rank, dev, steps, warmup, conf, ops_csv=None, time_all=False):
+def measure(name, world, rank, dev, steps, warmup, conf, ops_csv=None, time_all=False, outputs=None):
     """One config: warmup, K timed steps (barrier + synchronize on both sides, max over ranks), per-operator HIP
-    event timings -> rooflines. Returns (result dict, predictor)."""
+    event timings -> rooflines. Returns (result dict, predictor). ``outputs``: a dict that receives what the last
+    timed step returned (out / counts / index of predict_padded, CPU tensors) and, from one more forward on the same
+    batch after the region, the Detect output those detections were cut from (``pred``)."""
     cfg_yaml, imgsz, bs, label, dtype = CONFIGS[name]
     dname = DTYPE_NAME[dtype]
     model = build_model(cfg_yaml, seed=0, device=dev, dtype=dtype)
@@ -253,8 +278,8 @@ def measure(name, world, rank, dev, steps, warmup, conf, ops_csv=None, time_all=
         # the timed step is the same at every N: no host sync inside it. The split-range guard's flag word is read
         # once after the timed region on every rank (split_range_flagged below), not per step
         if world > 1:  # shard -> rank-local predict -> all-gather of the padded detections + kept indices
-            return sharded_predict(predictor.predict_padded, n_global, lambda a, b: x, split_guard=False)[1]
-        return predictor.predict_padded(x)[1]
+            return sharded_predict(predictor.predict_padded, n_global, lambda a, b: x, split_guard=False)
+        return predictor.predict_padded(x)
 
     # HIP events bracket only the hot-path operators and what is billed to them (perf.PathSelect; --time-all-ops:
     # every launch); the last warmup step runs through the filter so that it knows the plain variants to time
@@ -270,6 +295,8 @@ def measure(name, world, rank, dev, steps, warmup, conf, ops_csv=None, time_all=
     torch.cuda.synchronize()
     log(f"[rank {rank}] {name}: warmup {warmup} steps {time.perf_counter() - t_w:.2f}s")
 
+    last = [None]  # what the most recent timed step returned: (out, counts, index)
+
     def timed():
         if world > 1:
             dist.barrier()
@@ -277,7 +304,7 @@ def measure(name, world, rank, dev, steps, warmup, conf, ops_csv=None, time_all=
         with _hip.op_timer(select) as timer:
             t0 = time.perf_counter()
             for _ in range(steps):
-                step()
+                last[0] = step()
             torch.cuda.synchronize()
             if world > 1:
                 dist.barrier()
@@ -299,6 +326,18 @@ def measure(name, world, rank, dev, steps, warmup, conf, ops_csv=None, time_all=
             elapsed, _, timer = timed()
         redone = True
     durs = timer.durations_ms()
+    if outputs is not None:
+        outputs.update(zip(("out", "counts", "index"), (t.cpu() for t in last[0])))
+        with torch.inference_mode():
+            if flagged:
+                with _hip.exact_fp32_matrix():
+                    y = model(predictor.preprocess(x))
+            else:
+                y = model(predictor.preprocess(x))
+        outputs["pred"] = (y[0] if isinstance(y, (list, tuple)) else y).float().cpu()
+        if dtype == torch.float32:  # leave no flag of this untimed forward behind for a later region
+            _hip.split_range_flag(reset=True, device=dev)
+    last[0] = None
 
     # per-operator live timings (HIP events on the launch stream) -> roofline of the dominant operator; the
     # producer billing uses the same region's launches only (perf.producer_billing)
@@ -428,6 +467,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", default="n640", choices=list(CONFIGS))
     ap.add_argument("--conf", type=float, default=0.25)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region also run NMS at controlled candidate loads, the m640 / n1280 "
+                         "blocks and the CPU baseline (N = 1 only); the --no-* options below drop one of them each")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned (out, counts, index) and a seeded sample of the "
+                         "Detect output they were cut from (pred) as DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-nms-load", action="store_true")
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the m640 / n1280 blocks (N = 1 only)")
@@ -465,19 +510,24 @@ def main():
         dist.init_process_group("nccl", device_id=dev)
 
     rows = [] if args.ops_csv and rank == 0 else None
+    outputs = {} if args.dump_outputs and rank == 0 else None
     head, predictor, cfg_yaml, imgsz = measure(args.config, world, rank, dev, args.steps, args.warmup, args.conf,
-                                               ops_csv=rows, time_all=args.time_all_ops)
+                                               ops_csv=rows, time_all=args.time_all_ops, outputs=outputs)
+    if outputs is not None:
+        dump_outputs(outputs, args.dump_outputs)
+        outputs = None
     result = {"metric": METRIC, "value": head["value"], "unit": "images/s", "n_gpus": world, "steps": args.steps,
               "warmup": args.warmup, "ms_per_step": head["ms_per_step"], "higher_is_better": True,
               "scaling": "weak", "vs_baseline": None}
     result.update({k: v for k, v in head.items() if k not in result})
     result["nms_loaded"] = None
     result["cpu_baseline"] = None
-    if not args.no_nms_load:  # after the timed region, same process: NMS at controlled candidate loads
+    # a plain run ends with the headline region; everything below it is part of --full
+    if args.full and not args.no_nms_load:  # after the timed region, same process: NMS at controlled candidate loads
         result["nms_loaded"] = nms_loaded(dev)
     del predictor
     torch.cuda.empty_cache()
-    if world == 1 and args.config == "n640" and not args.no_extra_configs:
+    if args.full and world == 1 and args.config == "n640" and not args.no_extra_configs:
         # configs[3] (n1280 bs 8) and configs[4] (m640 bf16 bs 64): their own timed regions, same contract
         result["configs"] = {}
         for name in EXTRA_CONFIGS:
@@ -486,7 +536,7 @@ def main():
             result["configs"][name] = sub
             del pred
             torch.cuda.empty_cache()
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             # m scale: ~4x the n model's CPU work per image - a smaller sample keeps the same ~10-30 s budget
             m_scale = cfg_yaml.startswith("yolov12m")

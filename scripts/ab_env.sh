@@ -6,8 +6,8 @@ TAG=$1; VAR=$2; VA=$3; VB=$4
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 for i in 1 2; do
-  env "$VAR=$VA" timeout -k 10 300 python -u bench.py --no-cpu-baseline > "$OUT/a$i.json" 2> "$OUT/a$i.err" || exit 1
-  env "$VAR=$VB" timeout -k 10 300 python -u bench.py --no-cpu-baseline > "$OUT/b$i.json" 2> "$OUT/b$i.err" || exit 1
+  env "$VAR=$VA" timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > "$OUT/a$i.json" 2> "$OUT/a$i.err" || exit 1
+  env "$VAR=$VB" timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > "$OUT/b$i.json" 2> "$OUT/b$i.err" || exit 1
 done
 python - "$OUT" <<'PY'
 import json, sys, glob, os

@@ -5,8 +5,8 @@ TAG=$1; CFG=$2; VAR=$3; VA=$4; VB=$5
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 for i in 1 2; do
-  env "$VAR=$VA" timeout -k 10 300 python -u bench.py --config $CFG --no-cpu-baseline --no-nms-load > "$OUT/a$i.json" 2> "$OUT/a$i.err" || exit 1
-  env "$VAR=$VB" timeout -k 10 300 python -u bench.py --config $CFG --no-cpu-baseline --no-nms-load > "$OUT/b$i.json" 2> "$OUT/b$i.err" || exit 1
+  env "$VAR=$VA" timeout -k 10 300 python -u bench.py --full --config $CFG --no-cpu-baseline --no-nms-load > "$OUT/a$i.json" 2> "$OUT/a$i.err" || exit 1
+  env "$VAR=$VB" timeout -k 10 300 python -u bench.py --full --config $CFG --no-cpu-baseline --no-nms-load > "$OUT/b$i.json" 2> "$OUT/b$i.err" || exit 1
 done
 python - "$OUT" <<'PY'
 import json, sys, glob, os

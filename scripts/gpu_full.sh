@@ -20,7 +20,7 @@ if [ "$2" != "--no-tests" ]; then
   grep -E "FAILED|ERROR|passed|failed" "$OUT/pytest.log" | tail -15
   [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc
 fi
-timeout -k 10 500 python -u bench.py --steps 20 --warmup 5 --detail-json "$OUT/bench_detail.json" \
+timeout -k 10 500 python -u bench.py --full --steps 20 --warmup 5 --detail-json "$OUT/bench_detail.json" \
   --ops-csv "$OUT/ops_calls.csv" > "$OUT/bench.json" 2> "$OUT/bench.err" \
   || { echo "bench failed"; tail -20 "$OUT/bench.err"; exit 1; }
 wc -c "$OUT/bench.json"

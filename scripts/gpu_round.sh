@@ -15,7 +15,7 @@ rc=$?
 grep -E "FAILED|ERROR|passed|failed" "$OUT/pytest.log" | tail -25
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || exit $rc   # 1 = test failures (keep benching); anything else = stop
 for c in $CONFIGS; do
-  timeout -k 10 400 python -u bench.py --config $c > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { echo "bench $c failed"; tail -20 "$OUT/bench_$c.err"; exit 1; }
+  timeout -k 10 400 python -u bench.py --full --config $c > "$OUT/bench_$c.json" 2> "$OUT/bench_$c.err" || { echo "bench $c failed"; tail -20 "$OUT/bench_$c.err"; exit 1; }
   cut -c1-600 "$OUT/bench_$c.json"
 done
 exit $rc

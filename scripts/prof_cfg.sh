@@ -5,7 +5,7 @@ TAG=$1; CFG=$2; shift 2
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
-timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof_$CFG" -o run -- python3 -u bench.py --config $CFG \
+timeout -k 10 400 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof_$CFG" -o run -- python3 -u bench.py --full --config $CFG \
   --no-cpu-baseline --no-nms-load "$@" > "$OUT/bench_${CFG}_rocprof.json" 2> "$OUT/bench_${CFG}_rocprof.err" || { echo "rocprof failed"; tail -20 "$OUT/bench_${CFG}_rocprof.err"; exit 1; }
 f=$(find "$OUT/prof_$CFG" -name '*kernel_stats.csv' | head -1)
 cp "$f" "$OUT/kernel_stats_$CFG.csv"

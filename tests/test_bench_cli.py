@@ -113,6 +113,73 @@ def test_launcher_starts_ranks_as_a_child(monkeypatch):
     assert seen["env"]["MASTER_ADDR"] == "127.0.0.1"
 
 
+def _run_main_stubbed(monkeypatch, capsys, argv):
+    """bench.main() on one rank with every measuring part stubbed; returns (parts that ran, the printed line)."""
+    ran = []
+    full = _full_result()
+    head = {k: full[k] for k in ("value", "unit", "ms_per_step", "dtype", "data", "config", "roofline",
+                                 "path_roofline", "split_range_flagged", "hip_ops_ms_per_step", "hip_ops",
+                                 "backbone_hip_ms_per_step", "backbone_hip_ops")}
+
+    def measure(name, *a, outputs=None, **k):
+        ran.append(name)
+        if outputs is not None:
+            outputs.update(out=torch.zeros(2, 300, 6), counts=torch.zeros(2, dtype=torch.int32))
+        return dict(head), object(), "yolov12-sod-fusion-v5-simple.yaml", 640
+
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    monkeypatch.setattr(bench, "measure", measure)
+    monkeypatch.setattr(bench, "nms_loaded", lambda dev: ran.append("nms_loaded") or full["nms_loaded"])
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: ran.append("cpu_baseline") or full["cpu_baseline"])
+    monkeypatch.setattr(torch.cuda, "set_device", lambda *a: None)
+    monkeypatch.setattr(torch.cuda, "empty_cache", lambda: None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--detail-json", "", *argv])
+    bench.main()
+    return ran, json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+
+
+def test_plain_run_times_the_headline_only(monkeypatch, capsys, tmp_path):
+    """A plain run measures the headline config and nothing else; its line keeps the contract fields, and
+    --dump-outputs writes the arrays of that one region."""
+    ran, line = _run_main_stubbed(monkeypatch, capsys, ["--gpus", "1", "--steps", "7", "--warmup", "2",
+                                                        "--dump-outputs", str(tmp_path / "d")])
+    assert ran == ["n640"]
+    assert (line["steps"], line["warmup"], line["ms_per_step"], line["value"]) == (7, 2, 16.68, 1918.0)
+    assert (line["metric"], line["unit"], line["higher_is_better"], line["dtype"]) == (bench.METRIC, "images/s",
+                                                                                      True, "f32")
+    assert line["cpu_baseline"] is None and line["nms_loaded_ms_per_call"] is None and "configs" not in line
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == ["counts.npy", "out.npy"]
+
+
+def test_full_run_keeps_every_block(monkeypatch, capsys):
+    """--full: NMS at load, the extra configs and the CPU baseline after the headline, each with its --no-* switch."""
+    ran, line = _run_main_stubbed(monkeypatch, capsys, ["--full"])
+    assert ran == ["n640", "nms_loaded", *bench.EXTRA_CONFIGS, "cpu_baseline"]
+    assert line["cpu_baseline"]["value"] == 6.8 and set(line["configs"]) == set(bench.EXTRA_CONFIGS)
+    assert line["nms_loaded_ms_per_call"] == {str(n): 0.18 for n in bench.NMS_LOADS}
+    ran, _ = _run_main_stubbed(monkeypatch, capsys, ["--full", "--no-nms-load", "--no-cpu-baseline"])
+    assert ran == ["n640", *bench.EXTRA_CONFIGS]
+
+
+def test_dump_outputs_is_a_fixed_float_sample(tmp_path):
+    """Arrays above DUMP_SAMPLE elements are cut to the same seeded positions on every call; floats are written as
+    float32 and integer arrays as float64; small arrays whole."""
+    import numpy as np
+    big = torch.arange(bench.DUMP_SAMPLE * 3, dtype=torch.float32).reshape(3, -1)
+    outs = {"pred": big, "index": torch.arange(-1, 5, dtype=torch.int32), "half": torch.ones(4, dtype=torch.bfloat16)}
+    bench.dump_outputs(outs, tmp_path / "a")
+    bench.dump_outputs({k: v.clone() for k, v in outs.items()}, tmp_path / "b")
+    a = {p.stem: np.load(p) for p in (tmp_path / "a").iterdir()}
+    b = {p.stem: np.load(p) for p in (tmp_path / "b").iterdir()}
+    assert set(a) == set(b) == set(outs)
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    assert a["pred"].dtype == np.float32 and a["pred"].shape == (bench.DUMP_SAMPLE,)
+    assert np.all(np.diff(a["pred"]) >= 0) and a["pred"].max() > 2 * bench.DUMP_SAMPLE  # sorted, spans the array
+    assert a["index"].dtype == np.float64 and a["index"].tolist() == [-1, 0, 1, 2, 3, 4]
+    assert a["half"].dtype == np.float32
+    assert sum(v.nbytes for v in a.values()) < 64 << 20
+
+
 def _free_port():
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
