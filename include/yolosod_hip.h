@@ -133,6 +133,14 @@ int yolosod_bias_act_capool(const float* y, long y_bstride, float* out, long out
  * elem_bytes 4 (fp32) / 2 (bf16); w % 4 == 0 and 16-byte aligned pointers / strides. */
 int yolosod_upsample2x(const void* x, void* out, long out_bstride, int B, int C, int h, int w, int elem_bytes,
                        void* stream);
+/* The stem (layer 0: Conv 3 -> Cout, 3x3, stride 2, pad 1, SiLU) as one streaming pass: out [B, Cout, H/2, W/2] =
+ * SiLU(conv(x [B, 3, H, W], w [Cout, 3, 3, 3]) + bias), contiguous fp32, exact fp32 FMAs in (ci, ky, kx) order, plus
+ * the output's per-plane partial sums psum [B * Cout * parts] in the yolosod_plane_parts(H/2 * W/2) segmentation for
+ * the SE that follows (as yolosod_bias_act_stats emits them). H even, (W/2) % 4 == 0, Cout even and <= 64, x / out
+ * 16-byte aligned; workspace: yolosod_stem_workspace bytes of tile partials. Deterministic (no atomics). */
+size_t yolosod_stem_workspace(int B, int Cout, int H, int W);
+int yolosod_stem_conv(const float* x, const float* w, const float* bias, float* out, int B, int Cout, int H, int W,
+                      int parts, long seg, float* psum, void* workspace, size_t workspace_bytes, void* stream);
 int yolosod_ca_forward_pre(const float* x, float* y, int B, int C, int H, int W, const float* conv1_w,
                            const float* conv1_b, int mip, const float* bn_w, const float* bn_b, const float* bn_mean,
                            const float* bn_var, float bn_eps, const float* convh_w, const float* convh_b,
@@ -229,10 +237,12 @@ int yolosod_conv1x1_thin(const float* x, long x_bs, const float* w, const float*
 int yolosod_sppf_pool(float* z, long z_bstride, int B, int C, int H, int W, void* stream);
 
 /* yolosod_conv1x1_thin (no res) over a virtual concat [x; x2]: channels [0, k1) from x, [k1, Cin) from x2 (any split);
- * bit-identical to the materialised concat. */
+ * bit-identical to the materialised concat. up_w != 0: x is the quarter-size source [k1][H/2][up_w/2] of a nearest 2x
+ * upsample, read in place at (y >> 1, x >> 1); up_w = the output width W (W % 4 == 0, H = HW / W even); bit-identical
+ * to the upsampled-and-concatenated input. */
 int yolosod_conv1x1_thin_cat(const float* x, long x_bs, const float* x2, long x2_bs, int k1, const float* w,
                              const float* bias, float* out, long out_bs, float* out2, long out2_bs, int c2lo, int B,
-                             int Cin, int Cout, long HW, void* stream);
+                             int Cin, int Cout, long HW, int up_w, void* stream);
 
 /* yolosod_conv1x1_thin (no res / out2) that also emits the output's per-plane statistics for a following SE / CBAM
  * gate in the psum / pmax[B*Cout*parts] layout of yolosod_se_forward_pre / yolosod_cbam_forward_pre (parts =
@@ -324,10 +334,12 @@ int yolosod_conv1x1x2_silu(const float* x, long x_bstride, float* y, long y_bstr
                            size_t prep_bytes, void* stream);
 /* The same over a virtual concat [x; x2] (block.py:249-253: the C2f cv1 after a neck Concat): channels [0, k1) from x
  * (image b at x + b*x_bstride), [k1, cin) from x2 (image b at x2 + b*x2_bstride), k1 a multiple of 128; x2 NULL:
- * yolosod_conv1x1x2_silu. Bit-identical to the materialised concat. */
+ * yolosod_conv1x1x2_silu. Bit-identical to the materialised concat. up_w != 0 (needs x2): x is the quarter-size source
+ * [k1][H/2][up_w/2] of a nearest 2x upsample, read in place at (y >> 1, x >> 1); up_w = the output width W (W and
+ * H = HW / W even); bit-identical to the upsampled-and-concatenated input. */
 int yolosod_conv1x1x2_silu_cat(const float* x, long x_bstride, const float* x2, long x2_bstride, int k1, float* y,
                                long y_bstride, float* y2, long y2_bstride, int c2lo, int B, int cin, int cout, int HW,
-                               const float* bias, const void* prep, size_t prep_bytes, void* stream);
+                               const float* bias, const void* prep, size_t prep_bytes, int up_w, void* stream);
 /* Timing hook: ablation variants of the stride-2 conv kernel at Cout 64 with a channel gate (csrc/conv3x3s2.hip; WRONG
  * results for abl != 0 - scripts/bench_conv3x3s2.py only). Returns the previous value. */
 int yolosod_debug_set_conv3x3s2_abl(int abl);

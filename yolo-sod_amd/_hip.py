@@ -51,6 +51,8 @@ SIGNATURES = {
     "yolosod_attention": (_i, [_vp, _vp, _l, _i, _i, _i, _vp]),
     "yolosod_bias_act": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _l, _i, _vp]),
     "yolosod_upsample2x": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
+    "yolosod_stem_workspace": (_sz, [_i, _i, _i, _i]),
+    "yolosod_stem_conv": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _vp, _vp, _sz, _vp]),
     "yolosod_conv1x1_thin_stats": (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _l, _i, _vp, _vp, _vp, _vp]),
     "yolosod_conv1x1_thin": (_i, [_vp, _l, _vp, _vp, _vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _l, _vp]),
     "yolosod_bias_act_dual": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _vp, _l, _i, _i, _i, _l, _i, _vp]),
@@ -70,9 +72,9 @@ SIGNATURES = {
     "yolosod_conv1x1x2_prepare": (_i, [_vp, _i, _i, _vp, _sz, _vp]),
     "yolosod_conv1x1x2_silu": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "yolosod_conv1x1x2_silu_cat": (_i, [_vp, _l, _vp, _l, _i, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _sz,
-                                        _vp]),
+                                        _i, _vp]),
     "yolosod_sppf_pool": (_i, [_vp, _l, _i, _i, _i, _i, _vp]),
-    "yolosod_conv1x1_thin_cat": (_i, [_vp, _l, _vp, _l, _i, _vp, _vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _l, _vp]),
+    "yolosod_conv1x1_thin_cat": (_i, [_vp, _l, _vp, _l, _i, _vp, _vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _l, _i, _vp]),
     "yolosod_conv3x3_prep_bytes_ex": (_sz, [_i, _i]),
     "yolosod_conv3x3_prepare_ex": (_i, [_vp, _i, _i, _vp, _sz, _vp]),
     "yolosod_conv3x3_silu_ex": (_i, [_vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
@@ -678,6 +680,40 @@ def bias_act(y, bias, act, out=None, res=None, stats=None, out2=None, c2lo=0):
     return out
 
 
+STEM_TILE_ROWS = 8  # output rows per workgroup tile of csrc/stem.hip
+
+
+def stem_ok(x, conv) -> bool:
+    """Shapes the stem kernel takes (yolosod_stem_conv): a fused (bias-carrying) 3 -> Cout 3x3 / stride-2 / pad-1 conv
+    on a contiguous fp32 GPU batch with even H, W and Wout % 4 == 0, Cout even and <= 64. Everything else (bf16, odd
+    sizes, other Cin, CPU tensors, an un-fused Conv) keeps the MIOpen + epilogue path."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.device.type != "cuda" or x.dtype != torch.float32:
+        return False
+    B, Cin, H, W = x.shape
+    if (conv.bias is None or Cin != 3 or conv.in_channels != 3 or conv.kernel_size != (3, 3) or conv.stride != (2, 2)
+            or conv.padding != (1, 1) or conv.dilation != (1, 1) or conv.groups != 1
+            or conv.padding_mode != "zeros" or conv.weight.dtype != torch.float32 or conv.weight.device != x.device):
+        return False
+    Cout = conv.out_channels
+    if Cout % 2 or Cout > 64 or B == 0 or H % 2 or W % 2 or (W // 2) % 4:
+        return False
+    if not x.is_contiguous() or x.data_ptr() % 16:
+        return False
+    parts, seg = plane_parts((H // 2) * (W // 2))
+    return parts == 1 or STEM_TILE_ROWS * (W // 2) <= seg  # a tile meets at most two plan segments
+
+
+def stem_conv(x, weight, bias):
+    """out = SiLU(conv3x3 / stride 2 / pad 1 (x, weight) + bias) for x [B, 3, H, W] fp32 in one HIP pass (exact fp32
+    FMAs, csrc/stem.hip), with the output's per-plane partial sums attached as ``_ys_plane_stats`` (PlaneStats) for
+    the SE that follows, as ``bias_act(stats="sum")`` attaches them (torch.ops.yolosod.stem_fwd). Shapes: ``stem_ok``."""
+    B, _, H, W = _t(x, "x").shape
+    Cout = int(weight.shape[0])
+    out, psum = _launch(("stem", tuple(x.shape), (Cout, "sum")), x.device, ops().stem_fwd, x, weight, bias)
+    out._ys_plane_stats = PlaneStats(psum, None, plane_parts((H // 2) * (W // 2))[0], out.shape)
+    return out
+
+
 def upsample2x_into(x, out) -> bool:
     """Nearest 2x upsample of x [B, C, h, w] (contiguous, fp32 / bf16) into ``out`` [B, C, 2h, 2w], a channel slice
     of a Concat buffer (contiguous channels, any batch stride): the neck's ``nn.Upsample`` + ``Concat`` glue
@@ -706,7 +742,7 @@ def conv1x1_thin_ok(x, cout) -> bool:
     if isinstance(x, CatView):  # any split; both parts fp32 on the GPU with contiguous images
         B, Cin, H, W = x.shape
         return (x.device.type == "cuda" and x.dtype == torch.float32 and cout in THIN1X1_COUT and Cin in THIN1X1_CIN
-                and (H * W) % 64 == 0 and all(_imgs_contig(t) for t in x.parts))
+                and (H * W) % 64 == 0 and all(_imgs_contig(t) for t in x.parts) and (not x.up0 or W % 4 == 0))
     B, Cin, H, W = x.shape
     return (x.device.type == "cuda" and x.dtype == torch.float32 and cout in THIN1X1_COUT and Cin in THIN1X1_CIN
             and (H * W) % 64 == 0 and x.stride(3) == 1 and x.stride(2) == W and x.stride(1) == H * W
@@ -738,11 +774,17 @@ def conv1x1_thin(x, w, bias, out=None, res=None, out2=None, c2lo=0, stats=None):
         k1 = int(x0.shape[1])
         ob = bstride(out, "out", Cout)
         o2 = bstride(out2, "out2", Cout - c2lo) if out2 is not None else 0
+        if x.up0:  # part 0 is the quarter-size source of a nearest 2x upsample, addressed in place (CatView checked it)
+            if not _imgs_contig(x0) or W % 4:
+                raise RuntimeError("conv1x1_thin: an upsampled CatView part needs contiguous images and W % 4 == 0")
+            xb0 = x0.stride(0)
+        else:
+            xb0 = bstride(x0, "x", k1)
         _check(_launch(("conv1x1_thin", tuple(x.shape), (Cout, False, out2 is not None, "cat")), x.device,
-                       lib.yolosod_conv1x1_thin_cat, x0.data_ptr(), bstride(x0, "x", k1), x1.data_ptr(),
+                       lib.yolosod_conv1x1_thin_cat, x0.data_ptr(), xb0, x1.data_ptr(),
                        bstride(x1, "x2", Cin - k1), k1, _dev(w.contiguous(), "weight"), _dev(bias, "bias"),
                        out.data_ptr(), ob, None if out2 is None else out2.data_ptr(), o2, int(c2lo), B, Cin, Cout, HW,
-                       _stream(x.device)), "conv1x1_thin_cat")
+                       W if x.up0 else 0, _stream(x.device)), "conv1x1_thin_cat")
         return out
     xb = bstride(x, "x", Cin)
     ob = bstride(out, "out", Cout)
@@ -859,21 +901,29 @@ class CatView:
     """A two-part channel concat left unmaterialised: [B, C0 + C1, H, W] as its parts. A neck Concat whose only reader
     is the next C2f's cv1 (a 1x1 conv) hands this over, and the 1x1 kernels read both parts in place
     (yolosod_conv1x1x2_silu_cat / yolosod_conv1x1_thin_cat) instead of a materialised concat (block.py:249-253,
-    conv.py:336-340: the conv of a concat = the sum of the convs of its parts over their channel ranges)."""
+    conv.py:336-340: the conv of a concat = the sum of the convs of its parts over their channel ranges).
+    ``up0``: part 0 stands for the nearest 2x upsample of the tensor given ([B, C0, H/2, W/2]: the neck's nn.Upsample
+    feeding the Concat, never written out): the 1x1 kernels address it at (y >> 1, x >> 1); ``materialize()``
+    upsamples and concatenates, so every other reader sees the Concat's own output."""
 
-    def __init__(self, parts):
+    def __init__(self, parts, up0=False):
         a, b = parts
-        if a.shape[0] != b.shape[0] or a.shape[2:] != b.shape[2:] or a.dtype != b.dtype or a.device != b.device:
+        sp = (2 * a.shape[2], 2 * a.shape[3]) if up0 else tuple(a.shape[2:])
+        if a.shape[0] != b.shape[0] or sp != tuple(b.shape[2:]) or a.dtype != b.dtype or a.device != b.device:
             raise ValueError("CatView: parts must agree in batch, spatial size, dtype and device")
         self.parts = (a, b)
-        self.shape = torch.Size((a.shape[0], a.shape[1] + b.shape[1], a.shape[2], a.shape[3]))
+        self.up0 = bool(up0)
+        self.shape = torch.Size((a.shape[0], a.shape[1] + b.shape[1], b.shape[2], b.shape[3]))
         self.device, self.dtype = a.device, a.dtype
 
     def dim(self):
         return 4
 
     def materialize(self):
-        return torch.cat(self.parts, 1)
+        a, b = self.parts
+        if self.up0:
+            a = torch.nn.functional.interpolate(a, scale_factor=2, mode="nearest")
+        return torch.cat((a, b), 1)
 
 
 def sppf_pool(z, c):
@@ -945,7 +995,8 @@ def conv1x1x2_silu(x, bias, prep, cout, out=None, out2=None, c2lo=0):
                                               0 if x1 is None else x1.stride(0), int(x0.shape[1]), y.data_ptr(),
                                               y.stride(0), None if out2 is None else out2.data_ptr(),
                                               0 if out2 is None else out2.stride(0), int(c2lo), B, Cin, cout, H * W,
-                                              _dev(b, "bias"), blk.data_ptr(), blk.numel(), _stream(x.device))
+                                              _dev(b, "bias"), blk.data_ptr(), blk.numel(),
+                                              W if x1 is not None and x.up0 else 0, _stream(x.device))
 
     extra = (cout, out2 is not None) + (("cat",) if x1 is not None else ())
     _check(_launch(("conv1x1x2", tuple(x.shape), extra), x.device, run), "conv1x1x2")

@@ -98,6 +98,19 @@ __device__ __forceinline__ f32x2 gelu2_fast_(f32x2 x) {
 __device__ __forceinline__ float silu_fast_(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 __device__ __forceinline__ float sigmoid_fast_(float x) { return __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
+// SiLU of an epilogue value stored as T (conv_epilogue.hip, stem.hip): bf16 storage uses the hardware exp2 / rcp form
+// (error ~2^-22 relative, far below the bf16 rounding of the store; the libm expf + IEEE division made the bf16 passes
+// VALU-bound), fp32 storage the libm form (x / (1 + exp(-x)), the reference's arithmetic)
+template <class T>
+__device__ __forceinline__ float silu_st(float v) {
+#ifdef YS_FAST_SILU_F32  // A/B builds only: the fast form for fp32 storage too
+  return silu_fast_(v);
+#else
+  if constexpr (sizeof(T) == 2) return silu_fast_(v);
+  else return siluf_(v);
+#endif
+}
+
 // wave64 reductions
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -38,6 +38,8 @@ struct Args {
   const float* x2;     // optional second input (a virtual concat): channels [k1, Cin) at x2 + b x2bs ([Cin - k1][HW])
   long x2bs;
   int k1;              // channels taken from x (Cin when x2 is NULL; else a multiple of KS)
+  int up_w;            // != 0 (with x2): x is the quarter-size source [k1][H/2][up_w/2] of a nearest 2x upsample to
+                       // [k1][H][up_w], read in place at (y >> 1, x >> 1)
 };
 
 // NP pixels per tile (64 or 128: the weights are read from L2 once per tile, 128 halves that traffic)
@@ -68,30 +70,37 @@ __global__ __launch_bounds__(NT, 2) void conv1x1_x2_kernel(Args p) {
   // per stage (a select between two resource values is lowered to VGPRs, and every load then runs a waterfall loop)
   const float* xb1 = p.x + (long)b * p.xbs;
   const float* xb2 = p.x2 ? p.x2 + (long)b * p.x2bs : xb1;
-  const unsigned nb1 = (unsigned)((long)p.k1 * HW * 4), nb2 = (unsigned)((long)(p.cin - p.k1) * HW * 4);
+  // the first part's plane: HW floats, or the HW / 4 of the quarter-size source it is the nearest 2x upsample of
+  const int HW1 = p.up_w ? HW >> 2 : HW;
+  const unsigned nb1 = (unsigned)((long)p.k1 * HW1 * 4), nb2 = (unsigned)((long)(p.cin - p.k1) * HW * 4);
   const __amdgpu_buffer_rsrc_t rw = rsrc(p.wp, (unsigned)((long)nks * (p.cout >> 4) * 2 * 1024));
 
-  // staging item e = tid + NT i: channel quad e / NP (channels 4 quad .. + 3 of the stage), pixel e % NP (clamped
-  // to the image: pixels past HW load the last pixel, their outputs are not stored)
-  unsigned voff[NIT];
-#pragma unroll
-  for (int i = 0; i < NIT; ++i) {
-    const int e = tid + NT * i, quad = e / NP, px = e - quad * NP;
-    voff[i] = (unsigned)((4 * quad * HW + min(p0 + px, HW - 1)) * 4);
+  // staging item e = tid + NT i: channel quad e / NP = q0 + (NT / NP) i (channels 4 quad .. + 3 of the stage), pixel
+  // e % NP = tid % NP (clamped to the image: pixels past HW load the last pixel, their outputs are not stored)
+  static_assert(NT % NP == 0, "a thread stages one pixel");
+  const int q0 = tid / NP;
+  const int pc = min(p0 + tid % NP, HW - 1);
+  int pc1 = pc;  // the pixel's offset in a first-part plane: its source pixel (y >> 1, x >> 1) when that part is upsampled
+  if (p.up_w) {
+    const int yy = pc / p.up_w, xx = pc - yy * p.up_w;
+    pc1 = (yy >> 1) * (p.up_w >> 1) + (xx >> 1);
   }
   f32x4 sv[NIT];
   // the stage / channel offset is in the per-lane offset, so the buffer range check covers it: channels past Cin
   // (the last stage of a Cin that is not a multiple of KS) read 0, as do the padded weights they meet
   auto load_part = [&](int st, int k0, int k1, bool live) __attribute__((always_inline)) {
     const bool second = KS * st >= p.k1;  // stage-uniform
-    const unsigned sx = (unsigned)((second ? KS * st - p.k1 : KS * st) * HW * 4);
+    const int chs = second ? HW : HW1;    // plane stride of the part (scalar)
+    const unsigned sx = (unsigned)((second ? KS * st - p.k1 : KS * st) * chs * 4);
+    const unsigned vo = (unsigned)((4 * q0 * chs + (second ? pc : pc1)) * 4);
     // !live: an empty range (the last stage's "next stage" loads return 0 at once)
     const __amdgpu_buffer_rsrc_t r = rsrc(second ? xb2 : xb1, live ? (second ? nb2 : nb1) : 0u);
 #pragma unroll
     for (int k = 0; k < 4 * NIT; ++k)
       if (k >= k0 && k < k1)
         sv[k >> 2][k & 3] = __builtin_bit_cast(
-            float, __builtin_amdgcn_raw_buffer_load_b32(r, voff[k >> 2] + sx + (unsigned)((k & 3) * HW * 4), 0, 0));
+            float, __builtin_amdgcn_raw_buffer_load_b32(
+                       r, vo + sx + (unsigned)((4 * (NT / NP) * (k >> 2) + (k & 3)) * chs * 4), 0, 0));
   };
   // weight fragments of k step s (global), channel blocks cb0 + u, planes 0 / 1
   const int cb0 = grp * 4 * CPW + CPW * wid;
@@ -252,17 +261,22 @@ YS_EXPORT int yolosod_conv1x1x2_prepare(const float* w, int cin, int cout, void*
 // y = SiLU(W [x; x2] + bias): x image b at x + b x_bstride ([k1][HW]), x2 (or NULL) image b at x2 + b x2_bstride
 // ([cin - k1][HW]: the second part of a virtual concat, k1 a multiple of 128), y image b at y + b y_bstride
 // ([cout][HW]); y2 (or NULL): channels [c2lo, cout) stored again at y2 + b y2_bstride. HW % 4 == 0; 16-byte aligned
-// images.
+// images. up_w != 0 (with x2): x is the quarter-size source [k1][H/2][up_w/2] of a nearest 2x upsample (the neck's
+// nn.Upsample feeding the Concat), read in place at (y >> 1, x >> 1); up_w = the output width W (even, H = HW / W even).
+// Same values, staging layout and k order as the materialised form: bit-identical output.
 YS_EXPORT int yolosod_conv1x1x2_silu_cat(const float* x, long x_bstride, const float* x2, long x2_bstride, int k1,
                                          float* y, long y_bstride, float* y2, long y2_bstride, int c2lo, int B, int cin,
                                          int cout, int HW, const float* bias, const void* prep, size_t prep_bytes,
-                                         void* stream) {
+                                         int up_w, void* stream) {
   YS_CHECK_ARG(x && y && bias && prep, "conv1x1x2: null pointer");
   if (!x2) k1 = cin;
+  YS_CHECK_ARG(up_w == 0 || (x2 && up_w > 0 && up_w % 2 == 0 && HW % up_w == 0 && (HW / up_w) % 2 == 0),
+               "conv1x1x2: an upsampled first part needs a second part and even H, W (W=%d, HW=%d)", up_w, HW);
   YS_CHECK_ARG(k1 > 0 && k1 <= cin && (!x2 || (k1 % c1::KS == 0 && k1 < cin && x2_bstride >= (long)(cin - k1) * HW)),
                "conv1x1x2: concat split k1=%d (Cin %d) must be a multiple of %d", k1, cin, c1::KS);
   YS_CHECK_ARG(B >= 0 && HW > 0 && HW % 4 == 0 && yolosod_conv1x1x2_prep_bytes(cin, cout) > 0, "conv1x1x2: bad shape");
-  YS_CHECK_ARG(x_bstride >= (long)k1 * HW && y_bstride >= (long)cout * HW, "conv1x1x2: batch strides too small");
+  YS_CHECK_ARG(x_bstride >= (long)k1 * (up_w ? HW / 4 : HW) && y_bstride >= (long)cout * HW,
+               "conv1x1x2: batch strides too small");
   YS_CHECK_ARG((long)c1_pad(cin) * HW * 4 < (1L << 32), "conv1x1x2: image too large for 32-bit buffer offsets");
   YS_CHECK_ARG((((uintptr_t)y | (uintptr_t)(y2 ? y2 : y)) & 15) == 0 && y_bstride % 4 == 0 && y2_bstride % 4 == 0,
                "conv1x1x2: outputs must be 16-byte aligned");
@@ -276,7 +290,7 @@ YS_EXPORT int yolosod_conv1x1x2_silu_cat(const float* x, long x_bstride, const f
   constexpr int NPx = 64;  // pixels per tile (128-pixel tiles measured slower on four of five neck shapes)
   const int ntile = (HW + NPx - 1) / NPx;
   c1::Args a{x, x_bstride, wp, bias, y, y_bstride, y2, y2_bstride, c2lo, cin, cout, HW, ntile, range_flag_dev(), flag,
-             x2, x2_bstride, k1};
+             x2, x2_bstride, k1, up_w};
   const long nwg = (long)B * ntile * (cout == 64 ? 1 : cout / 128);
   YS_CHECK_ARG(nwg < (1L << 31), "conv1x1x2: too many tiles");
   hipStream_t st = (hipStream_t)stream;
@@ -296,5 +310,5 @@ YS_EXPORT int yolosod_conv1x1x2_silu(const float* x, long x_bstride, float* y, l
                                      long y2_bstride, int c2lo, int B, int cin, int cout, int HW, const float* bias,
                                      const void* prep, size_t prep_bytes, void* stream) {
   return yolosod_conv1x1x2_silu_cat(x, x_bstride, nullptr, 0, cin, y, y_bstride, y2, y2_bstride, c2lo, B, cin, cout, HW,
-                                    bias, prep, prep_bytes, stream);
+                                    bias, prep, prep_bytes, 0, stream);
 }

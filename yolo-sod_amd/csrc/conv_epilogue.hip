@@ -11,18 +11,7 @@
 
 namespace ys {
 
-// SiLU of an epilogue value: bf16 storage uses the hardware exp2 / rcp form (error ~2^-22 relative, far below the
-// bf16 rounding of the store; the libm expf + IEEE division made the bf16 passes VALU-bound), fp32 storage the
-// libm form (x / (1 + exp(-x)), the reference's arithmetic)
-template <class T>
-__device__ __forceinline__ float silu_st(float v) {
-#ifdef YS_FAST_SILU_F32  // A/B builds only: the fast form for fp32 storage too
-  return silu_fast_(v);
-#else
-  if constexpr (sizeof(T) == 2) return silu_fast_(v);
-  else return siluf_(v);
-#endif
-}
+// silu_st<T> (common.h): the SiLU of an epilogue value stored as T
 
 template <int ACT, bool RES, bool DUAL = false, class T = float>
 __global__ __launch_bounds__(256) void bias_act_kernel(const T* __restrict__ y, T* __restrict__ out,
@@ -276,7 +265,9 @@ __global__ __launch_bounds__(256) void bias_act_capool_kernel(const T* __restric
 // outputs of the 64 pixels; wave w owns output rows [w*M/4, (w+1)*M/4).
 // STATS: also the per-(plane, tile) sum and max of out in tsum/tmax[(b*M + row)*ntile + tile] (a following SE /
 // CBAM gate's statistics, reduced per plane by thin_stats_reduce_kernel).
-template <int M, int K, bool RES, bool DUAL, bool STATS = false>
+// UP (a virtual concat only): part 0 is the nearest 2x upsample of x ([k1][H/2][up_w/2] per image), read in place - a
+// 16-byte group of 4 output pixels is 2 source pixels, each used twice, and source rows serve two output rows.
+template <int M, int K, bool RES, bool DUAL, bool STATS = false, bool UP = false>
 __global__ __launch_bounds__(256, 2) void conv1x1_thin_kernel(const float* __restrict__ x, long x_bs,
                                                               const float* __restrict__ w,
                                                               const float* __restrict__ bias, float* __restrict__ out,
@@ -285,7 +276,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_thin_kernel(const float* __res
                                                               int ntile, int rev, float* __restrict__ tsum = nullptr,
                                                               float* __restrict__ tmax = nullptr,
                                                               const float* __restrict__ x2 = nullptr, long x2_bs = 0,
-                                                              int k1 = K) {
+                                                              int k1 = K, int up_w = 0) {
   constexpr int RB = M / 64;   // 16-row blocks per wave
   constexpr int KQ = K / 4;    // k quarter per lane group
   constexpr int XS = 68;       // LDS row stride (floats)
@@ -311,11 +302,31 @@ __global__ __launch_bounds__(256, 2) void conv1x1_thin_kernel(const float* __res
   for (int tile = blockIdx.x; tile < ntile; tile += gridDim.x) {
     const int p0 = tile * 64;
     __syncthreads();  // the previous tile's readers are done with xs
+    if (UP) {
+      // the source pixel pair of this thread's 4 output pixels (the same group for every row it stages); the two
+      // parts in loops of their own, so each keeps its (unrolled) loads in flight together
+      const int pp = p0 + 4 * (tid & 15), yy = pp / up_w, xx = pp - yy * up_w;
+      const float* xu = xb + (yy >> 1) * (up_w >> 1) + (xx >> 1);
+      const int hw1 = HW >> 2;
 #pragma unroll 4
-    for (int e = tid; e < K * 16; e += 256) {
-      const int row = e >> 4, c4 = e & 15;
-      *reinterpret_cast<float4*>(xs + row * XS + 4 * c4) =
-          *reinterpret_cast<const float4*>((row < k1 ? xb : xb2) + (long)row * HW + p0 + 4 * c4);
+      for (int e = tid; e < k1 * 16; e += 256) {
+        const int row = e >> 4, c4 = e & 15;
+        const float2 s2 = *reinterpret_cast<const float2*>(xu + (long)row * hw1);
+        *reinterpret_cast<float4*>(xs + row * XS + 4 * c4) = make_float4(s2.x, s2.x, s2.y, s2.y);
+      }
+#pragma unroll 4
+      for (int e = k1 * 16 + tid; e < K * 16; e += 256) {
+        const int row = e >> 4, c4 = e & 15;
+        *reinterpret_cast<float4*>(xs + row * XS + 4 * c4) =
+            *reinterpret_cast<const float4*>(xb2 + (long)row * HW + p0 + 4 * c4);
+      }
+    } else {
+#pragma unroll 4
+      for (int e = tid; e < K * 16; e += 256) {
+        const int row = e >> 4, c4 = e & 15;
+        *reinterpret_cast<float4*>(xs + row * XS + 4 * c4) =
+            *reinterpret_cast<const float4*>((row < k1 ? xb : xb2) + (long)row * HW + p0 + 4 * c4);
+      }
     }
     __syncthreads();
     f32x4 acc[RB][4];
@@ -682,9 +693,12 @@ YS_EXPORT int yolosod_conv1x1_thin(const float* x, long x_bs, const float* w, co
 
 // yolosod_conv1x1_thin over a virtual concat [x; x2] (channels [0, k1) from x, [k1, Cin) from x2), no residual /
 // statistics: the C2f cv1 after a neck Concat reads both parts in place instead of a materialised concat.
+// up_w != 0: x is the quarter-size source [k1][H/2][up_w/2] of a nearest 2x upsample (the neck's nn.Upsample feeding the
+// Concat) and is addressed at (y >> 1, x >> 1); up_w = the output width W (W % 4 == 0, H = HW / W even). Same values,
+// same summation order as the materialised form.
 YS_EXPORT int yolosod_conv1x1_thin_cat(const float* x, long x_bs, const float* x2, long x2_bs, int k1, const float* w,
                                        const float* bias, float* out, long out_bs, float* out2, long out2_bs, int c2lo,
-                                       int B, int Cin, int Cout, long HW, void* stream) {
+                                       int B, int Cin, int Cout, long HW, int up_w, void* stream) {
   YS_CHECK_ARG(x && x2 && w && bias && out, "conv1x1_thin_cat: null pointer");
   YS_CHECK_ARG(k1 > 0 && k1 < Cin, "conv1x1_thin_cat: k1=%d (Cin %d)", k1, Cin);
   YS_CHECK_ARG(HW % 64 == 0 && HW < (1L << 30), "conv1x1_thin_cat: HW=%ld must be a multiple of 64", HW);
@@ -694,6 +708,9 @@ YS_EXPORT int yolosod_conv1x1_thin_cat(const float* x, long x_bs, const float* x
   YS_CHECK_ARG((((uintptr_t)x | (uintptr_t)x2 | (uintptr_t)w | (uintptr_t)out) & 15) == 0,
                "conv1x1_thin_cat: pointers must be 16-byte aligned");
   YS_CHECK_ARG(!out2 || (c2lo >= 0 && c2lo < Cout), "conv1x1_thin_cat: c2lo=%d", c2lo);
+  YS_CHECK_ARG(up_w == 0 || (up_w > 0 && up_w % 4 == 0 && HW % up_w == 0 && (HW / up_w) % 2 == 0 &&
+                             x_bs >= (long)k1 * (HW / 4)),
+               "conv1x1_thin_cat: upsampled part needs W %% 4 == 0 and an even H (W=%d, HW=%ld)", up_w, HW);
   if (B == 0) return 0;
   const int ntile = (int)(HW / 64);
   const int gx = ntile < 4 ? ntile : (ntile + 3) / 4;
@@ -703,7 +720,13 @@ YS_EXPORT int yolosod_conv1x1_thin_cat(const float* x, long x_bs, const float* x
 #define YS_THINC(M_, K_)                                                                                          \
   if (Cout == M_ && Cin == K_) {                                                                                  \
     ok = true;                                                                                                    \
-    if (out2) hipLaunchKernelGGL((conv1x1_thin_kernel<M_, K_, false, true>), grid, dim3(256), 0, st, x, x_bs, w,    \
+    if (out2 && up_w) hipLaunchKernelGGL((conv1x1_thin_kernel<M_, K_, false, true, false, true>), grid, dim3(256), 0, st, x, x_bs, w, \
+                                 bias, out, out_bs, nullptr, 0L, out2, out2_bs, c2lo, (int)HW, ntile, mall_reverse(), \
+                                 nullptr, nullptr, x2, x2_bs, k1, up_w);                                           \
+    else if (up_w) hipLaunchKernelGGL((conv1x1_thin_kernel<M_, K_, false, false, false, true>), grid, dim3(256), 0, st, x, x_bs, w, bias, \
+                            out, out_bs, nullptr, 0L, nullptr, 0L, 0, (int)HW, ntile, mall_reverse(), nullptr, nullptr, \
+                            x2, x2_bs, k1, up_w);                                                                  \
+    else if (out2) hipLaunchKernelGGL((conv1x1_thin_kernel<M_, K_, false, true>), grid, dim3(256), 0, st, x, x_bs, w, \
                                  bias, out, out_bs, nullptr, 0L, out2, out2_bs, c2lo, (int)HW, ntile, mall_reverse(), \
                                  nullptr, nullptr, x2, x2_bs, k1);                                                 \
     else hipLaunchKernelGGL((conv1x1_thin_kernel<M_, K_, false, false>), grid, dim3(256), 0, st, x, x_bs, w, bias,  \

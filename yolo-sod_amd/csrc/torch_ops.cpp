@@ -425,6 +425,28 @@ std::tuple<Tensor, Tensor, Tensor> nms_batched(const Tensor& pred, double conf_t
   return {out, counts, index};
 }
 
+// The stem (layer 0): (SiLU(conv3x3 / stride 2 / pad 1 (x, weight) + bias), the output's plane partial sums for the SE
+// after it). fp32 only; the shapes are the caller's to check (_hip.stem_ok), the C ABI checks them again.
+std::tuple<Tensor, Tensor> stem_fwd(const Tensor& x, const Tensor& weight, const Tensor& bias) {
+  TORCH_CHECK(!act_bf16(x, "stem_fwd"), "stem_fwd: float32 activations only");
+  TORCH_CHECK(x.size(1) == 3 && weight.dim() == 4 && weight.size(1) == 3 && weight.size(2) == 3 && weight.size(3) == 3,
+              "stem_fwd: expected x [B, 3, H, W] and weight [Cout, 3, 3, 3]");
+  c10::DeviceGuard guard(x.device());
+  const int B = x.size(0), H = x.size(2), W = x.size(3), Cout = weight.size(0);
+  TORCH_CHECK(H % 2 == 0 && W % 2 == 0, "stem_fwd: even H and W required, got ", x.sizes());
+  Tensor out = at::empty({B, Cout, H / 2, W / 2}, x.options());
+  long seg = 0;
+  const int parts = yolosod_plane_parts((long)(H / 2) * (W / 2), &seg);
+  Tensor psum = at::empty({(int64_t)B * Cout * parts}, x.options());
+  Tensor ws = workspace(yolosod_stem_workspace(B, Cout, H, W), x);
+  auto st = c10::hip::getCurrentHIPStream(x.get_device());
+  check_rc(yolosod_stem_conv((const float*)x.data_ptr(), (const float*)par(weight, x, "weight", (int64_t)Cout * 27),
+                             (const float*)par(bias, x, "bias", Cout), (float*)out.data_ptr(), B, Cout, H, W, parts,
+                             seg, (float*)psum.data_ptr(), ws.data_ptr(), ws.numel(), sp(st)),
+           "stem_fwd");
+  return {out, psum};
+}
+
 // ---- shape-only (Meta) kernels ----
 Tensor mafn_meta(const Tensor& x) { return at::empty_like(x); }
 
@@ -456,6 +478,7 @@ TORCH_LIBRARY(yolosod, m) {
   m.def("detect_decode_fwd(Tensor[] maps, float[] strides, int nc, int reg_max) -> Tensor");
   m.def("nms_batched(Tensor(a!) pred, float conf_thres, float iou_thres, Tensor? classes, bool agnostic, "
         "bool multi_label, int max_det, int max_nms, float max_wh, bool in_place=True) -> (Tensor, Tensor, Tensor)");
+  m.def("stem_fwd(Tensor x, Tensor weight, Tensor bias) -> (Tensor, Tensor)");
 }
 
 TORCH_LIBRARY_IMPL(yolosod, CUDA, m) {
@@ -471,6 +494,7 @@ TORCH_LIBRARY_IMPL(yolosod, CUDA, m) {
   m.impl("detect_head_into", detect_head_into);
   m.impl("detect_decode_fwd", detect_decode_fwd);
   m.impl("nms_batched", nms_batched);
+  m.impl("stem_fwd", stem_fwd);
 }
 
 TORCH_LIBRARY_IMPL(yolosod, Meta, m) {
@@ -507,5 +531,11 @@ TORCH_LIBRARY_IMPL(yolosod, Meta, m) {
     auto f = pred.options();
     return std::make_tuple(at::empty({B, max_det, 6}, f), at::empty({B}, f.dtype(at::kInt)),
                            at::empty({B, max_det}, f.dtype(at::kInt)));
+  });
+  m.impl("stem_fwd", [](const Tensor& x, const Tensor& weight, const Tensor&) {
+    const int64_t B = x.size(0), C = weight.size(0), H = x.size(2) / 2, W = x.size(3) / 2;
+    long seg = 0;
+    const int parts = yolosod_plane_parts((long)(H * W), &seg);
+    return std::make_tuple(at::empty({B, C, H, W}, x.options()), at::empty({B * C * parts}, x.options()));
   });
 }

@@ -137,6 +137,10 @@ N1_NECK = os.environ.get("YOLOSOD_N1_NECK", "1") != "0"
 C2F_SLICES = os.environ.get("YOLOSOD_C2F_SLICES", "1") != "0"
 # SPPF's three chained max pools + concat as one HIP pass into the buffer cv1 writes (csrc/sppf.hip); 0: PyTorch
 SPPF_HIP = os.environ.get("YOLOSOD_SPPF_HIP", "1") != "0"
+# the stem (layer 0, 3 -> 32, 3x3 / stride 2, feeding SE L1) as one exact-fp32 HIP pass that also emits the SE's plane
+# sums (csrc/stem.hip) instead of MIOpen's Winograd kernel + the bias / SiLU / statistics pass; fp32 only, and it
+# stays on inside _hip.exact_fp32_matrix() (it is exact). YOLOSOD_STEM_HIP=0: MIOpen + epilogue
+STEM_HIP = os.environ.get("YOLOSOD_STEM_HIP", "1") != "0"
 
 
 def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, out2=None, c2lo=0, tower=False,
@@ -237,6 +241,8 @@ class Conv(nn.Module):
     s1 = False
     # set by DetectionModel on the neck's wide 1x1 convs: the fp16-split 1x1 kernel runs them (N1_NECK)
     n1 = False
+    # set by DetectionModel on layer 0 when it is a 3-channel 3x3 / stride-2 Conv feeding an SE: the stem kernel (STEM_HIP)
+    stem = False
 
     def __init__(self, c1, c2, k=1, s=1, p=None, g=1, d=1, act=True):
         super().__init__()
@@ -260,6 +266,9 @@ class Conv(nn.Module):
         return _hip.conv3x3s2_silu(x, cv.bias, prep, cv.out_channels, gate_c, gate_p, key=key)
 
     def forward_fuse(self, x, out=None, res=None, out2=None, c2lo=0):
+        if (self.stem and STEM_HIP and self.emit_stats == "sum" and out is None and res is None and out2 is None
+                and isinstance(self.act, nn.SiLU) and _hip.stem_ok(x, self.conv)):
+            return _hip.stem_conv(x, self.conv.weight.detach(), self.conv.bias.detach())
         y = conv_epilogue(self.conv, _act_code(self.act), x, out, res, self.emit_stats, out2, c2lo, self.tower,
                           self.s2, self.s1, self.n1)
         if y is not None:

@@ -59,6 +59,10 @@ UPSAMPLE_HIP = os.environ.get("YOLOSOD_UPSAMPLE_HIP", "1") != "0"
 # a _hip.CatView instead of a buffer: the skip input (an earlier layer's saved output) is not copied at all, the -1
 # producer writes its own tensor (YOLOSOD_CATVIEW=0: the concat buffer with the producer's slice written in place)
 CATVIEW = os.environ.get("YOLOSOD_CATVIEW", "1") != "0"
+# a nearest 2x Upsample that only feeds such a CatView is not run at all: the 1x1 kernel reading the CatView addresses the
+# quarter-size source at (y >> 1, x >> 1) (CatView(up0=True); fp32, bit-identical). YOLOSOD_UPVIEW=0: the upsample is
+# written out (its HIP pass) and read back
+UPVIEW = os.environ.get("YOLOSOD_UPVIEW", "1") != "0"
 
 # name -> class; the YAML resolves module strings through this (tasks.py:995-1002)
 DEFAULT_REGISTRY = {
@@ -278,7 +282,7 @@ class BaseModel(nn.Module):
             rr = 0  # next side stream (round robin over towers)
         y = []
         pend = {}  # concat index -> (buffer, channel offset of each input)
-        cvpend = {}  # concat index -> True: handed to the next C2f as a CatView
+        cvpend = {}  # concat index -> (part 0 is an Upsample's source,): handed to the next C2f as a CatView
         elided = 0
         gplan = self._gate_consumers() if GATE_FUSE else {}
         gated = None  # (gate input, channel gate, spatial gate, fused-op key) for the next layer
@@ -324,13 +328,18 @@ class BaseModel(nn.Module):
                         and all(s is None or (s.shape[0], s.shape[2], s.shape[3]) == (B, H, W) for s in srcs)
                         and M.catview_route(nxt.cv1, chans[0], chans[1], H, W, inp.dtype)):
                     # the Concat becomes a CatView of its inputs: the producer writes its own tensor
+                    up0 = False
                     if isinstance(m, nn.Upsample):
-                        x = torch.empty((B, cp, H, W), dtype=inp.dtype, device=inp.device)
-                        if not (UPSAMPLE_HIP and _hip.upsample2x_into(inp, x)):
-                            x = m(inp)
+                        if (UPVIEW and cat.f[0] == -1 and inp.dtype == torch.float32 and inp.is_contiguous()
+                                and inp.data_ptr() % 16 == 0 and W % 4 == 0):
+                            x, up0 = inp, True  # read in place by the CatView's 1x1 kernel: no upsample launch
+                        else:
+                            x = torch.empty((B, cp, H, W), dtype=inp.dtype, device=inp.device)
+                            if not (UPSAMPLE_HIP and _hip.upsample2x_into(inp, x)):
+                                x = m(inp)
                     else:
                         x = m(inp)
-                    cvpend[c] = True
+                    cvpend[c] = (up0,)
                     y.append(None)
                     continue
                 if all(s is None or (s.shape[0], s.shape[2], s.shape[3]) == (B, H, W) for s in srcs):
@@ -348,8 +357,9 @@ class BaseModel(nn.Module):
                     x = out
                     y.append(None)
                     continue
-            if cvpend.pop(m.i, False):
-                x = _hip.CatView([x if j == -1 else y[j] for j in m.f])
+            cvp = cvpend.pop(m.i, None)
+            if cvp is not None:
+                x = _hip.CatView([x if j == -1 else y[j] for j in m.f], up0=cvp[0])
                 elided += 1
             elif m.i in pend:
                 buf, offs, chans = pend.pop(m.i)
@@ -443,6 +453,14 @@ class DetectionModel(BaseModel):
                 if isinstance(conv, M.Conv):
                     conv.emit_stats = ("summax" if isinstance(m, M.CBAM_Block) else
                                        "capool" if isinstance(m, M.CA_Block) else "sum")
+
+        # layer 0 as the stem kernel (modules.STEM_HIP): a 3-channel 3x3 / stride-2 Conv whose output feeds the SE
+        # after it (the kernel emits that SE's plane sums; shapes are checked per call: _hip.stem_ok)
+        m0 = self.model[0]
+        if (isinstance(m0, M.Conv) and not isinstance(m0, M.DWConv) and m0.emit_stats == "sum"
+                and m0.conv.in_channels == 3 and m0.conv.kernel_size == (3, 3) and m0.conv.stride == (2, 2)
+                and m0.conv.groups == 1):
+            m0.stem = True
 
         # the neck's 3x3 / stride-2 convs run on the stride-2 fp16-split kernel (modules.S2_NECK); the backbone's
         # convs stay on PyTorch-ROCm (north_star), except SE L1's / CBAM L4's consumers, which apply those gates

@@ -174,6 +174,14 @@ def producer_of(key):
         cout = extra[0]
         plain = ("conv1x1_thin", tuple(shape), (cout, False, False)) + tail
         return PRODUCER_GATE[extra[1]], (B, cout, H, W), plain, B * H * W * (cin + cout) * E
+    if op == "stem" and isinstance(extra, tuple) and len(extra) == 2 and extra[1] in PRODUCER_GATE:
+        # the stem kernel (csrc/stem.hip) has no plain variant in the model: its plain pass is priced at the HBM roof of
+        # its own bytes (the image batch read once + the stride-2 map written once)
+        B, cin, H, W = shape
+        cout = extra[0]
+        plain = ("stem", tuple(shape), (cout, None)) + tail
+        nbytes = B * (cin * H * W + cout * (H // 2) * (W // 2)) * E
+        return PRODUCER_GATE[extra[1]], (B, cout, H // 2, W // 2), plain, nbytes
     return None
 
 
