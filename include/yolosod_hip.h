@@ -346,6 +346,16 @@ int yolosod_debug_set_conv3x3s2_abl(int abl);
 /* Timing hook: ablation variants of the 3x3 conv kernel (csrc/conv3x3.hip; WRONG results for any abl != 0 and
  * != 16 - scripts/bench_conv3x3.py only). Returns the previous value. */
 int yolosod_debug_set_conv3x3_abl(int abl);
+/* Test / measurement hook: force the form of the persistent 3x3 conv kernel (csrc/conv3x3.hip, W % 4 == 0 shapes);
+ * every form gives bit-identical results. form = geometry + 4 * groups. geometry: 0 automatic (the fewest tiles for
+ * the map), 1 the 32 x 8 tile of 16 x 1 blocks, 2 the 20 x 12 tile of 4 x 4 blocks, 3 the 40 x 6 tile of 8 x 2
+ * blocks. groups: 0 automatic (32-channel groups when 64-channel work items would leave workgroup slots idle), 1
+ * 64-channel output groups (an error for Cout 32), 2 32-channel groups. Values outside [0, 12) are ignored. Returns
+ * the previous value. */
+int yolosod_debug_set_conv3x3_form(int form);
+/* The form (same encoding, no field 0) a [B][*][H][W] -> cout launch of yolosod_conv3x3_silu* runs in under the current
+ * setting; 0 for shapes the persistent kernel does not take (W % 4 != 0, unsupported cout). */
+int yolosod_debug_conv3x3_form(int B, int cout, int H, int W);
 void yolosod_debug_set_gemm_x2(int on);
 /* Test hook: the bf16 decomposed SwinBlock's depthwise conv + token layout and LN1 in one pass
  * (swin_tokens_ln_bf16_kernel, 1, default) or as two kernels (0);

@@ -1,5 +1,7 @@
-"""Micro-benchmark: the Detect tower 3x3 convs at the n640 shapes (bs 32) on the fp16-split kernel vs MIOpen
-(F.conv2d without bias + the HIP bias / SiLU epilogue, as the executor runs it). GPU only."""
+"""Micro-benchmark: the stride-1 3x3 convs of the n640 step (bs 32) - the Detect towers and the backbone's / neck's C2f
+Bottleneck convs (Cout 32 .. 256, with and without the shortcut) - on the fp16-split kernel vs MIOpen (F.conv2d without
+bias + the HIP bias / SiLU (+ shortcut) epilogue, as the executor runs it). GPU only.
+python scripts/bench_conv3x3.py [forms | <abl>,...]; YOLOSOD_LIB_AB=<lib> times another build of the library."""
 import sys
 from pathlib import Path
 
@@ -29,7 +31,7 @@ def timed(fn, reps=50):
     return e0.elapsed_time(e1) / reps
 
 
-ABL = [int(a) for a in sys.argv[1].split(",")] if len(sys.argv) > 1 else []
+ABL = [int(a) for a in sys.argv[1].split(",")] if len(sys.argv) > 1 and sys.argv[1] != "forms" else []
 if ABL:  # timing ablations of the kernel (wrong results): see yolosod_debug_set_conv3x3_abl
     lib = _hip.load_library()
     for shape in SHAPES[:2]:
@@ -50,14 +52,40 @@ if ABL:  # timing ablations of the kernel (wrong results): see yolosod_debug_set
         lib.yolosod_debug_set_conv3x3_abl(0)
     sys.exit(0)
 
-for shape in SHAPES:
+# every stride-1 3x3 launch shape of the n640 step at bs 32: (input shape, Cout, residual). Detect towers (Cout 64),
+# then the C2f Bottleneck convs of the backbone (L3 / L6 / L8 / L11) and the neck (cv1 plain, cv2 + shortcut)
+CASES = [(s, 64, False) for s in SHAPES]
+for c, hw in ((32, 160), (64, 80), (128, 40), (256, 20)):
+    CASES += [((32, c, hw, hw), c, False), ((32, c, hw, hw), c, True)]
+# forms of the persistent kernel (yolosod_debug_set_conv3x3_form: geometry + 4 groups), when the library has the hook
+# (an older library given by YOLOSOD_LIB_AB has one form): "forms" as the first argument times every form per shape
+lib = _hip.load_library()
+FORMS = [0]
+if len(sys.argv) > 1 and sys.argv[1] == "forms" and hasattr(lib, "yolosod_debug_set_conv3x3_form"):
+    FORMS = [0] + [g + 4 * grp for g in (1, 2, 3) for grp in (1, 2)]
+GEO = {1: "32x8", 2: "20x12", 3: "40x6"}
+
+for shape, cout, res in CASES:
     B, cin, H, W = shape
     x = torch.randn(shape, device=dev)
-    w = torch.randn(64, cin, 3, 3, device=dev) * 0.05
-    b = torch.randn(64, device=dev) * 0.1
+    w = torch.randn(cout, cin, 3, 3, device=dev) * 0.05
+    b = torch.randn(cout, device=dev) * 0.1
+    r = torch.randn(B, cout, H, W, device=dev) if res else None
     prep = _hip.conv3x3_prepare(w)
-    t_k = timed(lambda: _hip.conv3x3_silu(x, b, lambda: prep))
-    t_m = timed(lambda: _hip.bias_act(F.conv2d(x, w, None, padding=1), b, 1))
-    gf = 2 * B * H * W * 64 * cin * 9 / 1e9
-    print(f"{str(shape):22s} kernel {t_k:7.3f} ms ({gf / t_k:6.1f} TF/s)   MIOpen+epilogue {t_m:7.3f} ms "
-          f"({gf / t_m:6.1f} TF/s)", flush=True)
+    gf = 2 * B * H * W * cout * cin * 9 / 1e9
+    t_m = timed(lambda: _hip.bias_act(F.conv2d(x, w, None, padding=1), b, 1, res=r))
+    line = f"{str(shape):22s} -> {cout:3d}{' +res' if res else '     '}  MIOpen+epilogue {t_m:7.3f} ms ({gf / t_m:6.1f} TF/s)"
+    for form in FORMS:
+        if form and cout == 32 and form >> 2 == 1:
+            continue
+        if len(FORMS) > 1:
+            lib.yolosod_debug_set_conv3x3_form(form)
+        t_k = timed(lambda: _hip.conv3x3_silu(x, b, lambda: prep, cout, res=r))
+        name = "kernel"
+        if hasattr(lib, "yolosod_debug_conv3x3_form"):
+            f = lib.yolosod_debug_conv3x3_form(B, cout, H, W)
+            name = f"{'auto=' if form == 0 else ''}{GEO[f & 3]}/g{32 * (3 - (f >> 2))}"
+        line += f"   {name} {t_k:6.3f} ms ({gf / t_k:5.1f} TF/s)"
+    if len(FORMS) > 1:
+        lib.yolosod_debug_set_conv3x3_form(0)
+    print(line, flush=True)

@@ -99,6 +99,8 @@ SIGNATURES = {
     "yolosod_debug_set_a2_fused": (_i, [_i]),
     "yolosod_debug_set_a2_pool_wide": (_i, [_i]),
     "yolosod_debug_set_conv3x3_abl": (_i, [_i]),
+    "yolosod_debug_set_conv3x3_form": (_i, [_i]),
+    "yolosod_debug_conv3x3_form": (_i, [_i, _i, _i, _i]),
     "yolosod_debug_set_conv3x3s2_abl": (_i, [_i]),
     "yolosod_se_gate": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "yolosod_cbam_gates": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -870,10 +872,11 @@ def _img_view(t, shape, name):
                            "contiguous 16-byte aligned images")
 
 
-def conv3x3_silu(x, bias, prep, cout=64, out=None, res=None):
+def conv3x3_silu(x, bias, prep, cout=64, out=None, res=None, op="conv3x3"):
     """SiLU(conv3x3(x) + bias) (+ res) on the fp16 two-term split MFMA (csrc/conv3x3.hip); ``prep`` is a callable
     returning the cached prepared block of the weights (conv3x3_prepare); ``out``: a [B, Cout, H, W] view with
-    contiguous images (a concat slice) to write; ``res``: the residual added after the activation (same shape)."""
+    contiguous images (a concat slice) to write; ``res``: the residual added after the activation (same shape);
+    ``op``: the op_timer key's name (the backbone's launches are recorded as "conv3x3_backbone")."""
     lib = load_library()
     B, Cin, H, W = x.shape
     if out is None:
@@ -893,7 +896,7 @@ def conv3x3_silu(x, bias, prep, cout=64, out=None, res=None):
                                            0 if res is None else res.stride(0), B, Cin, cout, H, W, _dev(b, "bias"),
                                            blk.data_ptr(), blk.numel(), _stream(x.device))
 
-    _check(_launch(("conv3x3", tuple(x.shape), cout if res is None else (cout, "res")), x.device, run), "conv3x3")
+    _check(_launch((op, tuple(x.shape), cout if res is None else (cout, "res")), x.device, run), "conv3x3")
     return y
 
 

@@ -244,8 +244,48 @@ __global__ __launch_bounds__(256, 2) void conv3x3_x2_kernel(Args p) {
 // (item, input chunk), and the next iteration's halo loads (the next tile's first chunk included) are spread over the
 // current iteration's taps, so no tile starts with an exposed HBM wait. Per-image buffer resources with unclamped
 // offsets (rows above the image are negative offsets: out of range, 0); other out-of-image pixels masked by okb.
-template <int CBW, bool RES>
+//
+// Geometry G (chosen per launch, c3_pick_geo): a lane holds pixels 4 g .. + 3 of a 16-pixel block, so a block may be
+// 16 x 1, 8 x 2 or 4 x 4 pixels (BW x BH) with the same 16-byte stores; a workgroup has 16 block slots (two row-halves
+// x 8 per wave) laid out as TBX x TBY blocks (a slot past TBX TBY recomputes block 0 and stores nothing). The order of
+// an output element's additions (chunk -> tap -> product) does not depend on G or CBW: every form is bit-identical.
+//   G 0: 16 x 1 blocks, 2 x 8: the 32 x 8 tile (P2 / P3), halo 34 x 10
+//   G 1:  4 x 4 blocks, 5 x 3: a 20 x 12 tile, halo 22 x 14 (20^2 maps: 78 % of the slots useful against 52 %)
+//   G 2:  8 x 2 blocks, 5 x 3: a 40 x 6 tile, halo 42 x 8 (40^2 maps: 89 % against 62.5 %)
+// RS: the LDS row stride in pixels. A ds_read_b128 is served in four groups of 16 lanes ({0-3, 12-15, 20-27}, {4-11,
+// 16-19, 28-31}, + 32), conflict-free when the group's sixteen 16-byte slots differ mod 16; with 6 slots per pixel
+// (PS = 48) a block row must start at slot 8 (mod 16) of the previous one's for 4 x 4 and at slot 0 for 8 x 2:
+// RS = 4 (mod 8) >= 22 -> 28, RS = 0 (mod 8) >= 42 -> 48 (tests/test_conv3x3_lds_banks.py enumerates them).
+template <int G>
+struct Geo;
+template <>
+struct Geo<0> {
+  static constexpr int BW = 16, TBX = 2, TBY = 8, RS = 34;
+};
+template <>
+struct Geo<1> {
+  static constexpr int BW = 4, TBX = 5, TBY = 3, RS = 28;
+};
+template <>
+struct Geo<2> {
+  static constexpr int BW = 8, TBX = 5, TBY = 3, RS = 48;
+};
+template <int G>
+struct GeoD : Geo<G> {
+  using B = Geo<G>;
+  static constexpr int BH = 16 / B::BW, NBLK = B::TBX * B::TBY;
+  static constexpr int TW = B::TBX * B::BW, TH = B::TBY * BH, HW_ = TW + 2, HH = TH + 2, NPXH = HH * HW_;
+  static constexpr int PL = HH * B::RS * PS;  // plane (halves)
+  static constexpr int NQUAD = NPXH * 8, NIT = (NQUAD + NT - 1) / NT;
+  static_assert(NBLK <= 16 && B::RS >= HW_ && NIT <= 11 && HW_ < 256 && HH < 256, "conv3x3 geometry");
+};
+
+template <int G, int CBW, bool RES>
 __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
+  using Ge = GeoD<G>;
+  constexpr int BW = Ge::BW, BH = Ge::BH, TBX = Ge::TBX, NBLK = Ge::NBLK, RS = Ge::RS;
+  constexpr int TH = Ge::TH, TW = Ge::TW, HH = Ge::HH, HW_ = Ge::HW_, NPXH = Ge::NPXH, PL = Ge::PL;
+  constexpr int NQUAD = Ge::NQUAD, NIT = Ge::NIT;
   __shared__ __attribute__((aligned(16))) h16_t Pl[2 * PL];
   __shared__ float bsh[512];  // every output channel's bias: an epilogue load would wait behind the prefetches
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -326,7 +366,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
   const int rp = wid & 1, ph = wid >> 1;
   int bpx[8];
 #pragma unroll
-  for (int cb = 0; cb < 8; ++cb) bpx[cb] = (4 * ph + (cb >> 1)) * HW_ + (cb & 1) * 16 + l15;
+  for (int cb = 0; cb < 8; ++cb) {
+    const int bi = 8 * ph + cb < NBLK ? 8 * ph + cb : 0;  // a slot past the tile's blocks recomputes block 0, unstored
+    bpx[cb] = ((bi / TBX) * BH + l15 / BW) * RS + (bi % TBX) * BW + l15 % BW;
+  }
   auto wfrag = [&](int t, int q, int cbw, int pl) __attribute__((always_inline)) {
     const int st = __builtin_amdgcn_readfirstlane(((t * nq + q) * p.ncb_all * 2) * 1024);
     return __builtin_bit_cast(f16x8_t, __builtin_amdgcn_raw_buffer_load_b128(
@@ -350,7 +393,8 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
     for (int i = 0; i < NIT; ++i) {
       const int e = tid + NT * i;
       if (e < NQUAD) {
-        const int quad = pk[i] >> 16, px = e - quad * NPXH;
+        const int quad = pk[i] >> 16;
+        const int px = RS == HW_ ? e - quad * NPXH : ((pk[i] >> 8) & 255) * RS + (pk[i] & 255);
         const f32x4 v = ((okb >> i) & 1u) ? sv[i] : f32x4{0.f, 0.f, 0.f, 0.f};
         uint2 hh, ll;
         split4x(v, hh, ll);
@@ -374,7 +418,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
     // keep each step's two LDS reads ahead of the previous step's MFMAs: without them the reads sit right before
     // their use and every block waits an LDS round trip
     auto rd = [&](int t, int cb, f16x8_t& h, f16x8_t& l) __attribute__((always_inline)) {
-      const h16_t* src = Pl + (bpx[cb] + (t / 3) * HW_ + (t % 3)) * PS + 8 * g;
+      const h16_t* src = Pl + (bpx[cb] + (t / 3) * RS + (t % 3)) * PS + 8 * g;
       h = *reinterpret_cast<const f16x8_t*>(src);
       l = *reinterpret_cast<const f16x8_t*>(src + PL);
     };
@@ -421,7 +465,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
       for (int u = 0; u < CBW; ++u) bv[u] = bsh[16 * (cbw0 + u) + l15];
 #pragma unroll
       for (int cb = 0; cb < 8; ++cb) {
-        const int oy = r.ty * TH + 4 * ph + (cb >> 1), ox = r.tx * TW + (cb & 1) * 16 + 4 * g;
+        const int bi = 8 * ph + cb;
+        const int oy = r.ty * TH + (bi / TBX) * BH + (4 * g) / BW, ox = r.tx * TW + (bi % TBX) * BW + (4 * g) % BW;
+        const bool live = (NBLK == 16 || bi < NBLK) && oy < H && ox < W;
 #pragma unroll
         for (int u = 0; u < CBW; ++u) {
           const long po = (long)(16 * (cbw0 + u) + l15) * HWi + oy * W + ox;
@@ -430,9 +476,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
           for (int e = 0; e < 4; ++e) o[e] = silu_fast_(acc[u][cb][e] * (1.0f / WSC) + bv[u]);
           if constexpr (RES) {
 #pragma clang fp contract(off)  // a separately rounded add, as x + cv2(...): no fma with SiLU's last multiply
-            if (oy < H && ox < W) o = o + *reinterpret_cast<const f32x4*>(p.res + (long)r.b * p.rbs + po);
+            if (live) o = o + *reinterpret_cast<const f32x4*>(p.res + (long)r.b * p.rbs + po);
           }
-          if (oy < H && ox < W) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(yb + po));
+          if (live) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(yb + po));
           acc[u][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
       }
@@ -476,6 +522,33 @@ YS_EXPORT int yolosod_debug_set_conv3x3_abl(int abl) {
   return old;
 }
 
+// Forced form of the persistent kernel (tests / per-shape measurements compare forms; the automatic choice is the
+// product): form = geometry + 4 groups; geometry 0 automatic, 1 the 32 x 8 tile, 2 the 20 x 12 tile of 4 x 4 blocks,
+// 3 the 40 x 6 tile of 8 x 2 blocks; groups 0 automatic, 1 64-channel output groups, 2 32-channel groups. Every
+// geometry takes every W % 4 == 0 shape; 64-channel groups need Cout >= 64. Returns the previous value.
+static int g_c3_form = 0;
+YS_EXPORT int yolosod_debug_set_conv3x3_form(int form) {
+  const int old = g_c3_form;
+  if (form >= 0 && form < 12) g_c3_form = form;
+  return old;
+}
+
+static const int C3_GEO_TW[3] = {c3::GeoD<0>::TW, c3::GeoD<1>::TW, c3::GeoD<2>::TW};
+static const int C3_GEO_TH[3] = {c3::GeoD<0>::TH, c3::GeoD<1>::TH, c3::GeoD<2>::TH};
+
+// The geometry with the fewest tiles (every tile is 16 block slots of MFMA work, useful or not) for an H x W map; the
+// 32 x 8 tile on a tie and for every map above 40 x 40 (P2 / P3: the form those shapes were tuned on).
+static int c3_pick_geo(int H, int W) {
+  if ((long)H * W > 1600) return 0;
+  int best = 0;
+  long nbest = 0;
+  for (int g = 0; g < 3; ++g) {
+    const long n = (long)((W + C3_GEO_TW[g] - 1) / C3_GEO_TW[g]) * ((H + C3_GEO_TH[g] - 1) / C3_GEO_TH[g]);
+    if (g == 0 || n < nbest) best = g, nbest = n;
+  }
+  return best;
+}
+
 static int c3_cu_count() {
   static int n = 0;
   if (n == 0) {
@@ -486,6 +559,17 @@ static int c3_cu_count() {
     n = c;
   }
   return n;
+}
+
+// The resolved form (geometry 1 .. 3 + 4 * groups 1 .. 2) of a W % 4 == 0 launch: the forced fields of g_c3_form, the
+// automatic choice for the others. 32-channel groups (twice the work items, each with half the MFMAs and its own
+// staging) when the 64-channel items would leave workgroup slots (two per CU) idle.
+static int c3_form(int B, int cout, int H, int W) {
+  const int fgeo = g_c3_form & 3, fgrp = (g_c3_form >> 2) & 3;
+  const int geo = fgeo ? fgeo - 1 : c3_pick_geo(H, W);
+  const long ntiles = (long)B * ((W + C3_GEO_TW[geo] - 1) / C3_GEO_TW[geo]) * ((H + C3_GEO_TH[geo] - 1) / C3_GEO_TH[geo]);
+  const bool g32 = cout == 32 || (fgrp ? fgrp == 2 : ntiles * (cout / 64) < 2L * c3_cu_count());
+  return geo + 1 + 4 * (g32 ? 2 : 1);
 }
 
 static bool c3_cout_ok(int cout) { return cout == 32 || (cout % 64 == 0 && cout <= 512); }
@@ -499,6 +583,13 @@ YS_EXPORT size_t yolosod_conv3x3_prep_bytes_ex(int cin, int cout) {
   return s.off;
 }
 YS_EXPORT size_t yolosod_conv3x3_prep_bytes(int cin) { return yolosod_conv3x3_prep_bytes_ex(cin, 64); }
+
+// The form (as yolosod_debug_set_conv3x3_form encodes it, no field 0) the persistent kernel runs a [B][*][H][W] ->
+// cout launch in under the current setting; 0 for shapes it does not take (W % 4 != 0, unsupported cout).
+YS_EXPORT int yolosod_debug_conv3x3_form(int B, int cout, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0 || W % 4 || !c3_cout_ok(cout)) return 0;
+  return c3_form(B, cout, H, W);
+}
 
 static bool conv3x3_carve(void* buf, size_t bytes, int cin, int cout, h16_t** wp, unsigned** flag) {
   Carver cv(buf, bytes);
@@ -561,13 +652,28 @@ YS_EXPORT int yolosod_conv3x3_silu_xs(const float* x, long x_bstride, float* y, 
   hipStream_t st = (hipStream_t)stream;
   // the persistent kernel for W % 4 == 0 (two workgroups per CU); the one-tile-per-workgroup kernel otherwise
   if (v4 && g_c3_abl == 0) {
+    const int fgrp = (g_c3_form >> 2) & 3;
+    YS_CHECK_ARG(!(fgrp == 1 && cout == 32), "conv3x3: 32 outputs have no 64-channel group form");
+    const int form = c3_form(B, cout, H, W);
+    const int geo = (form & 3) - 1;
+    const bool g32 = (form >> 2) == 2;
+    a.tiles_x = (W + C3_GEO_TW[geo] - 1) / C3_GEO_TW[geo];
+    a.tiles_y = (H + C3_GEO_TH[geo] - 1) / C3_GEO_TH[geo];
     a.ntiles = (int)((long)B * a.tiles_x * a.tiles_y);
-    long grid = 2L * c3_cu_count();
-    grid = grid < ((nwg + 7) / 8) * 8 ? grid : ((nwg + 7) / 8) * 8;
+    const long slots = 2L * c3_cu_count();
+    const long nitems = (long)a.ntiles * (g32 ? cout / 32 : cout / 64);
+    YS_CHECK_ARG(nitems < (1L << 31), "conv3x3: too many tiles");
+    long grid = slots < ((nitems + 7) / 8) * 8 ? slots : ((nitems + 7) / 8) * 8;
     grid = (grid + 7) / 8 * 8;
-    auto pk = cout == 32 ? (res ? c3::conv3x3_p_kernel<1, true> : c3::conv3x3_p_kernel<1, false>)
-                         : (res ? c3::conv3x3_p_kernel<2, true> : c3::conv3x3_p_kernel<2, false>);
-    hipLaunchKernelGGL(pk, dim3((unsigned)grid), dim3(256), 0, st, a);
+    using KP = void (*)(c3::Args);
+    static const KP kp[3][2][2] = {
+        {{c3::conv3x3_p_kernel<0, 2, false>, c3::conv3x3_p_kernel<0, 2, true>},
+         {c3::conv3x3_p_kernel<0, 1, false>, c3::conv3x3_p_kernel<0, 1, true>}},
+        {{c3::conv3x3_p_kernel<1, 2, false>, c3::conv3x3_p_kernel<1, 2, true>},
+         {c3::conv3x3_p_kernel<1, 1, false>, c3::conv3x3_p_kernel<1, 1, true>}},
+        {{c3::conv3x3_p_kernel<2, 2, false>, c3::conv3x3_p_kernel<2, 2, true>},
+         {c3::conv3x3_p_kernel<2, 1, false>, c3::conv3x3_p_kernel<2, 1, true>}}};
+    hipLaunchKernelGGL(kp[geo][g32 ? 1 : 0][res ? 1 : 0], dim3((unsigned)grid), dim3(256), 0, st, a);
     YS_CHECK_LAUNCH("conv3x3");
     return 0;
   }

@@ -126,9 +126,18 @@ CONV3X3 = os.environ.get("YOLOSOD_CONV3X3", "1")
 # and P4 -> P5) on the stride-2 fp16-split kernel (csrc/conv3x3s2.hip), writing straight into their Concat slice,
 # instead of MIOpen's NHWC implicit GEMM with its layout transposes + the bias / SiLU pass; YOLOSOD_S2_NECK=0: MIOpen
 S2_NECK = os.environ.get("YOLOSOD_S2_NECK", "1") != "0"
+# the backbone's gate-free 3x3 / stride-2 convs (layers 7 / 10: 128 -> 256 at 80^2 and 256 -> 512 at 40^2 at the paper
+# scale) on the same kernel (0.164 / 0.129 ms against 0.381 / 0.334 ms for MIOpen's NHWC implicit GEMM + layout
+# transposes + the bias / SiLU pass); YOLOSOD_S2_BACKBONE=0: MIOpen
+S2_BACKBONE = os.environ.get("YOLOSOD_S2_BACKBONE", "1") != "0"
 # the PAN neck's C2f Bottleneck 3x3 convs (layers 17 / 22 / 27 / 31 / 35 / 38) on the fp16-split stride-1 kernel, the
 # shortcut added and the output written into the C2f concat slice in its epilogue; YOLOSOD_S1_NECK=0: MIOpen
 S1_NECK = os.environ.get("YOLOSOD_S1_NECK", "1") != "0"
+# the backbone C2fs' Bottleneck 3x3 convs (layers 3 / 6 / 8 / 11: ten convs at the paper scale) on the same kernel in
+# the same way, instead of MIOpen's Winograd kernel + the bias / SiLU / shortcut pass: YOLOSOD_S1_BACKBONE=1. Off by
+# default: it shortens the n640 step by 1.05 ms, but on the e2e noisy scenes its worst box coordinate (0.146 px against
+# fp64) uses more than half of what the MIOpen path (0.131 px) leaves below the 0.158 px bound
+S1_BACKBONE = os.environ.get("YOLOSOD_S1_BACKBONE", "0") == "1"
 # the PAN neck's wide 1x1 convs (Cout a multiple of 128: C2f cv1 / cv2, lateral convs) on the fp16-split 1x1 kernel
 # (csrc/conv1x1x2.hip) with bias / SiLU / concat slice / C2f's dual store in its epilogue; YOLOSOD_N1_NECK=0: MIOpen
 N1_NECK = os.environ.get("YOLOSOD_N1_NECK", "1") != "0"
@@ -143,6 +152,16 @@ SPPF_HIP = os.environ.get("YOLOSOD_SPPF_HIP", "1") != "0"
 STEM_HIP = os.environ.get("YOLOSOD_STEM_HIP", "1") != "0"
 
 
+def _s2_on(s2) -> bool:
+    """Whether a Conv's stride-2 mark (False / True: neck / "backbone") routes it to the stride-2 fp16-split kernel."""
+    return bool(s2) and (S2_BACKBONE if s2 == "backbone" else S2_NECK)
+
+
+def _s1_on(s1) -> bool:
+    """Whether a Conv's ``s1`` mark (False / True: neck / "backbone") routes it to the stride-1 fp16-split kernel."""
+    return bool(s1) and (S1_BACKBONE if s1 == "backbone" else S1_NECK)
+
+
 def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, out2=None, c2lo=0, tower=False,
                   s2=False, s1=False, n1=False):
     """GPU fast path of ``act(conv(x)) (+ res)``: MIOpen conv without bias, then one HIP pass for bias +
@@ -151,8 +170,10 @@ def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, 
     SE / CBAM gate (``_hip.PlaneStats`` on the returned tensor).
     ``out2``: also store channels [c2lo, C) packed there (the next conv's input; C2f's Bottleneck chain).
     ``tower``: the conv is one of the Detect head's 3x3 tower convs (the fp16-split conv kernel takes it).
-    ``s2``: the conv is one of the neck's 3x3 / stride-2 convs (the stride-2 fp16-split kernel takes it).
-    ``s1``: one of the neck's C2f Bottleneck 3x3 convs (the stride-1 fp16-split kernel, with out / res).
+    ``s2``: the conv is one of the 3x3 / stride-2 convs the stride-2 fp16-split kernel takes: True for the neck's
+    (S2_NECK), "backbone" for the backbone's gate-free ones (S2_BACKBONE).
+    ``s1``: one of the C2f Bottleneck 3x3 convs (the stride-1 fp16-split kernel, with out / res): True for the neck's
+    (S1_NECK), "backbone" for the backbone's (S1_BACKBONE).
     ``n1``: one of the neck's wide 1x1 convs (the fp16-split 1x1 kernel, with out / out2).
     Returns None when the fast path does not apply (CPU tensor, no bias, unsupported activation / shape)."""
     if x.device.type != "cuda" or conv.bias is None or act_code is None or x.dtype not in (torch.float32,
@@ -179,14 +200,16 @@ def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, 
             and (out is None or _hip._imgs_contig(out)) and (out2 is None or _hip._imgs_contig(out2))):
         prep = lambda: _cached(conv, "c1prep", (conv.weight,), lambda: _hip.conv1x1x2_prepare(conv.weight))  # noqa: E731
         return _hip.conv1x1x2_silu(x, conv.bias, prep, conv.out_channels, out=out, out2=out2, c2lo=c2lo)
-    if (split and s1 and S1_NECK and act_code == 1 and stats is None and out2 is None and _hip.conv3x3_ok(x, conv)
+    if (split and _s1_on(s1) and act_code == 1 and stats is None and out2 is None and _hip.conv3x3_ok(x, conv)
             and x.shape[3] % 4 == 0 and (res is None or _hip._imgs_contig(res))):
         prep = lambda: _cached(conv, "c3prep", (conv.weight,), lambda: _hip.conv3x3_prepare(conv.weight))  # noqa: E731
-        return _hip.conv3x3_silu(x, conv.bias, prep, conv.out_channels, out=out, res=res)
-    if (split and s2 and S2_NECK and act_code == 1 and res is None and stats is None and out2 is None
+        return _hip.conv3x3_silu(x, conv.bias, prep, conv.out_channels, out=out, res=res,
+                                 op="conv3x3_backbone" if s1 == "backbone" else "conv3x3")
+    if (split and _s2_on(s2) and act_code == 1 and res is None and stats is None and out2 is None
             and _hip.conv3x3s2_ok(x, conv)):
         prep = lambda: _cached(conv, "c3s2prep", (conv.weight,), lambda: _hip.conv3x3s2_prepare(conv.weight))  # noqa: E731
-        return _hip.conv3x3s2_silu(x, conv.bias, prep, conv.out_channels, out=out)
+        key = ("conv3x3s2_backbone", tuple(x.shape), (conv.out_channels, False, False)) if s2 == "backbone" else None
+        return _hip.conv3x3s2_silu(x, conv.bias, prep, conv.out_channels, key=key, out=out)
     if (THIN1X1 and act_code == 1 and (stats is None or (stats in ("sum", "summax") and res is None and out2 is None))
             and conv.out_channels == 64 and conv.kernel_size == (1, 1) and conv.stride == (1, 1)
             and conv.groups == 1 and conv.padding == (0, 0) and _hip.conv1x1_thin_ok(x, conv.out_channels)
@@ -237,8 +260,12 @@ class Conv(nn.Module):
     tower = False
     # set by DetectionModel on the neck's 3x3 / stride-2 convs: the stride-2 fp16-split kernel runs them (S2_NECK)
     s2 = False
+    # set by DetectionModel on the backbone's gate-free 3x3 / stride-2 convs: the same kernel runs them (S2_BACKBONE)
+    s2_backbone = False
     # set by DetectionModel on the neck's C2f Bottleneck 3x3 convs: the stride-1 fp16-split kernel runs them (S1_NECK)
     s1 = False
+    # set by DetectionModel on the backbone's C2f Bottleneck 3x3 convs: the same kernel runs them (S1_BACKBONE)
+    s1_backbone = False
     # set by DetectionModel on the neck's wide 1x1 convs: the fp16-split 1x1 kernel runs them (N1_NECK)
     n1 = False
     # set by DetectionModel on layer 0 when it is a 3-channel 3x3 / stride-2 Conv feeding an SE: the stem kernel (STEM_HIP)
@@ -270,7 +297,7 @@ class Conv(nn.Module):
                 and isinstance(self.act, nn.SiLU) and _hip.stem_ok(x, self.conv)):
             return _hip.stem_conv(x, self.conv.weight.detach(), self.conv.bias.detach())
         y = conv_epilogue(self.conv, _act_code(self.act), x, out, res, self.emit_stats, out2, c2lo, self.tower,
-                          self.s2, self.s1, self.n1)
+                          "backbone" if self.s2_backbone else self.s2, self.s1_mark(), self.n1)
         if y is not None:
             return y
         if isinstance(x, _hip.CatView):
@@ -287,6 +314,10 @@ class Conv(nn.Module):
 
     def is_fused(self):
         return not hasattr(self, "bn")
+
+    def s1_mark(self):
+        """conv_epilogue's ``s1`` of this Conv: "backbone" (S1_BACKBONE), True (S1_NECK) or False."""
+        return "backbone" if self.s1_backbone else self.s1
 
 
 class DWConv(Conv):
@@ -343,8 +374,12 @@ class C2f(nn.Module):
             # each Bottleneck's input also lands packed in `t` (dual-store epilogue): MIOpen reads packed tensors,
             # so a channel slice of z would cost a copy pass per Bottleneck
             z = torch.empty((B, (2 + n) * c, H, W), dtype=x.dtype, device=x.device)
-            if (n and S1_NECK and C2F_SLICES and _hip.split_convs_enabled() and x.dtype == torch.float32 and W % 4 == 0
-                    and all(m.cv1.s1 and m.cv2.s1 and m.cv1.conv.kernel_size == (3, 3) for m in self.m)):
+            # (C2F_SLICES=0 restores the neck's dual-store form; the backbone's Bottlenecks have no such form on the
+            # kernel - a chain of n > 1 needs the packed second store - and S1_BACKBONE=0 is their A/B switch)
+            if (n and _hip.split_convs_enabled() and x.dtype == torch.float32 and W % 4 == 0
+                    and (C2F_SLICES or all(m.cv1.s1_backbone and m.cv2.s1_backbone for m in self.m))
+                    and all(_s1_on(m.cv1.s1_mark()) and _s1_on(m.cv2.s1_mark()) and m.cv1.conv.kernel_size == (3, 3)
+                            for m in self.m)):
                 # the Bottlenecks run on the stride-1 fp16-split kernel, which reads channel slices: each one reads
                 # its input in place from z (no packed second store)
                 self.cv1.forward_fuse(x, out=z[:, : 2 * c])

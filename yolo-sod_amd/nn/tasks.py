@@ -462,18 +462,25 @@ class DetectionModel(BaseModel):
                 and m0.conv.groups == 1):
             m0.stem = True
 
-        # the neck's 3x3 / stride-2 convs run on the stride-2 fp16-split kernel (modules.S2_NECK); the backbone's
-        # convs stay on PyTorch-ROCm (north_star), except SE L1's / CBAM L4's consumers, which apply those gates
+        # the neck's 3x3 / stride-2 convs run on the stride-2 fp16-split kernel (modules.S2_NECK); the backbone's other
+        # convs stay on PyTorch-ROCm, except SE L1's / CBAM L4's consumers, which apply those gates, its gate-free
+        # 3x3 / stride-2 convs (modules.S2_BACKBONE) and its C2fs' Bottleneck convs (modules.S1_BACKBONE)
         n_backbone = len(self.yaml.get("backbone", []))
         for i, m in enumerate(self.model):
-            if (i >= n_backbone and isinstance(m, M.Conv) and not isinstance(m, M.DWConv)
+            if (isinstance(m, M.Conv) and not isinstance(m, M.DWConv)
                     and m.conv.kernel_size == (3, 3) and m.conv.stride == (2, 2) and m.conv.groups == 1):
-                m.s2 = True
-            if i >= n_backbone and isinstance(m, M.C2f):  # the neck C2fs' Bottleneck 3x3 convs (S1_NECK)
+                if i >= n_backbone:
+                    m.s2 = True
+                elif i and m.f == -1 and not isinstance(self.model[i - 1], (M.SE, M.CBAM_Block)):
+                    m.s2_backbone = True  # gate-free (not the stem, not an SE / CBAM consumer): modules.S2_BACKBONE
+            if isinstance(m, M.C2f):  # the C2fs' Bottleneck 3x3 convs (neck: S1_NECK, backbone: S1_BACKBONE)
                 for bt in m.m:
                     for cv in (bt.cv1, bt.cv2):
                         if cv.conv.kernel_size == (3, 3) and cv.conv.stride == (1, 1) and cv.conv.groups == 1:
-                            cv.s1 = True
+                            if i >= n_backbone:
+                                cv.s1 = True
+                            else:
+                                cv.s1_backbone = True
             # the neck's wide 1x1 convs (N1_NECK): lateral Convs and the C2fs' cv1 / cv2
             if i >= n_backbone:
                 for cv in ([m] if isinstance(m, M.Conv) and not isinstance(m, M.DWConv) else
