@@ -190,6 +190,24 @@ int yolosod_nms(float* pred, int B, int nc, int A, float conf_thres, double iou_
                 int n_classes, int agnostic, int multi_label, int max_det, int max_nms, float max_wh, int in_place,
                 float* out, int* counts, int* out_index, void* workspace, size_t workspace_bytes, void* stream);
 
+/* BasePredictor.preprocess, non-tensor branch + LetterBox   ultralytics/engine/predictor.py:116-134, pre_transform
+ * :145-161 (LetterBox: ultralytics/data/augment.py, restated in yolo-sod_amd/data/augment.py), one launch per batch.
+ * desc: device int64 [B][8] = source address, h, w, row pitch in bytes, new_h, new_w, top, left of each frame: uint8
+ * HWC, 3 bytes per pixel in B, G, R order, pitch >= 3*w (a cropped view is a valid frame), h and w <= 16384; frames
+ * of one batch may differ in size. The kernel reads whole aligned dwords that hold a byte of the frame.
+ * out: [B][3][out_h][out_w] RGB planes, image b at out + b*out_bstride elements (out_bstride % 4 == 0), fp32 or
+ * (out_bf16) bf16 bit patterns, out_w % 4 == 0, 16-byte aligned; every element is written: the frame resized to
+ * new_h x new_w at (top, left) (integer bilinear, csrc/ingest.hip; value = float(q) / 255.0f, bf16 rounded once
+ * more to nearest even), pad_value / 255 elsewhere. Deterministic. */
+int yolosod_letterbox_ingest(const int64_t* desc, int B, void* out, long out_bstride, int out_h, int out_w,
+                             int out_bf16, int pad_value, void* stream);
+/* DetectionPredictor.postprocess -> scale_boxes   ultralytics/models/yolo/detect/predict.py:23-41,
+ * ultralytics/utils/ops.py:92-128 (clip_boxes :319-338) on the padded NMS output with per-image geometry, no host
+ * sync. det: [B][D][6]; geom: device float [B][5] = gain, pad_x, pad_y, w0, h0. Rows < counts[b]: columns 0..3
+ * become (v - pad) / gain (IEEE division) clamped to [0, w0] / [0, h0]; rows >= counts[b] and columns 4, 5 are not
+ * touched. D in 1..2^20. */
+int yolosod_scale_boxes(float* det, const int* counts, int B, int D, const float* geom, void* stream);
+
 /* Conv epilogue for the PyTorch-ROCm backbone convs (not a reference hot-path op; conv.py:37-55 + block.py:343-356
  * + Concat): out[b*out_bstride + c*HW + p] = act(y[b*y_bstride + c*HW + p] + bias[c]) (+ res[...]); act 0 id, 1 SiLU.
  * Writes into channel slices of a concat buffer via out_bstride; in place allowed. */

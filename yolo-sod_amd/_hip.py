@@ -51,6 +51,8 @@ SIGNATURES = {
     "yolosod_attention": (_i, [_vp, _vp, _l, _i, _i, _i, _vp]),
     "yolosod_bias_act": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _l, _i, _vp]),
     "yolosod_upsample2x": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
+    "yolosod_letterbox_ingest": (_i, [_vp, _i, _vp, _l, _i, _i, _i, _i, _vp]),
+    "yolosod_scale_boxes": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "yolosod_stem_workspace": (_sz, [_i, _i, _i, _i]),
     "yolosod_stem_conv": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _vp, _vp, _sz, _vp]),
     "yolosod_conv1x1_thin_stats": (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _l, _i, _vp, _vp, _vp, _vp]),
@@ -1069,6 +1071,90 @@ def conv3x3s2_silu(x, bias, prep, cout, gate_c=None, gate_p=None, key=None, out=
         key = ("conv3x3s2", tuple(x.shape), (cout, gc is not None, gp is not None))
     _check(_launch(key, x.device, run), "conv3x3s2")
     return y
+
+
+INGEST_MAX_DIM = 16384  # source / canvas extents of csrc/ingest.hip (32-bit arithmetic, 14-bit index fields)
+
+
+def letterbox_ingest(images, out_shape, geoms, dtype=torch.float32, out=None, pad_value=114):
+    """Raw frames -> the model's input tensor in one launch (yolosod_letterbox_ingest): ``images`` is a sequence of
+    uint8 GPU tensors [h, w, 3] in BGR order (sizes may differ; a row-cropped / column-cropped view is fine: pixel
+    stride 3, channel stride 1, any row pitch >= 3 w), ``geoms[i]`` = (new_h, new_w, top, left, ...) as
+    ``LetterBox.geometry`` returns it, ``out_shape`` = (out_h, out_w) of the canvas. Returns [B, 3, out_h, out_w]
+    RGB / 255 in ``dtype`` (float32 or bfloat16), border ``pad_value`` / 255. ``out``: write into this
+    [B, 3, out_h, out_w] tensor instead (contiguous images, any batch stride that is a multiple of 4).
+
+    The descriptor the kernel reads is built here from each tensor's own ``data_ptr()``, shape and strides only, and
+    everything the kernel relies on is checked here: nothing is launched on a frame that fails."""
+    lib = load_library()
+    B = len(images)
+    out_h, out_w = int(out_shape[0]), int(out_shape[1])
+    if B < 1 or len(geoms) != B:
+        raise RuntimeError(f"letterbox_ingest: {B} frames with {len(geoms)} geometries")
+    if dtype not in (torch.float32, _BF16):
+        raise RuntimeError(f"letterbox_ingest: output dtype must be float32 or bfloat16, got {dtype}")
+    if out_w % 4 or not (0 < out_h <= INGEST_MAX_DIM and 0 < out_w <= INGEST_MAX_DIM):
+        raise RuntimeError(f"letterbox_ingest: canvas {out_h}x{out_w} unsupported (width % 4 == 0, <= {INGEST_MAX_DIM})")
+    rows = []
+    dev = None
+    for i, (t, g) in enumerate(zip(images, geoms)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"letterbox_ingest: frame {i}: expected a tensor")
+        if t.dtype != torch.uint8:
+            raise RuntimeError(f"letterbox_ingest: frame {i}: expected uint8, got {t.dtype}")
+        if t.dim() != 3 or t.shape[2] != 3:
+            raise RuntimeError(f"letterbox_ingest: frame {i}: expected [h, w, 3] (BGR), got {tuple(t.shape)}")
+        h, w = int(t.shape[0]), int(t.shape[1])
+        if not (0 < h <= INGEST_MAX_DIM and 0 < w <= INGEST_MAX_DIM):
+            raise RuntimeError(f"letterbox_ingest: frame {i}: {h}x{w} outside 1..{INGEST_MAX_DIM}")
+        if t.stride(2) != 1:
+            raise RuntimeError(f"letterbox_ingest: frame {i}: channel stride {t.stride(2)} (1 expected)")
+        if w > 1 and t.stride(1) != 3:
+            raise RuntimeError(f"letterbox_ingest: frame {i}: pixel stride {t.stride(1)} (3 expected)")
+        pitch = int(t.stride(0)) if h > 1 else 3 * w
+        if pitch < 3 * w:
+            raise RuntimeError(f"letterbox_ingest: frame {i}: row pitch {pitch} < 3 * {w}")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"letterbox_ingest: frame {i}: HIP kernel requires a GPU tensor (got device "
+                               f"{t.device}); no CPU fallback")
+        if dev is None:
+            dev = t.device
+        elif t.device != dev:
+            raise RuntimeError(f"letterbox_ingest: frame {i} on {t.device}, frame 0 on {dev}")
+        nh, nw, top, left = (int(v) for v in g[:4])
+        if nh < 1 or nw < 1 or top < 0 or left < 0 or top + nh > out_h or left + nw > out_w:
+            raise RuntimeError(f"letterbox_ingest: frame {i}: geometry {tuple(g)} leaves the {out_h}x{out_w} canvas")
+        rows.append([t.data_ptr(), h, w, pitch, nh, nw, top, left])
+    if out is None:
+        out = torch.empty((B, 3, out_h, out_w), dtype=dtype, device=dev)
+    elif (out.dtype != dtype or out.device != dev or tuple(out.shape) != (B, 3, out_h, out_w)
+          or out.stride()[1:] != (out_h * out_w, out_w, 1) or out.stride(0) % 4 or out.stride(0) < 3 * out_h * out_w
+          or out.data_ptr() % 16):
+        raise RuntimeError(f"letterbox_ingest: out must be a {dtype} [{B}, 3, {out_h}, {out_w}] tensor on {dev} with "
+                           "contiguous 16-byte aligned images and a batch stride that is a multiple of 4")
+    desc = torch.tensor(rows, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+    key = ("ingest", (B, 3, out_h, out_w), 2 if dtype == _BF16 else None)
+    _check(_launch(key, dev, lib.yolosod_letterbox_ingest, desc.data_ptr(), B, out.data_ptr(), out.stride(0) if B > 1
+                   else 3 * out_h * out_w, out_h, out_w, int(dtype == _BF16), int(pad_value), _stream(dev)),
+           "letterbox_ingest")
+    return out
+
+
+def scale_boxes_padded(out, counts, geom):
+    """The padded NMS rows back to each frame's own pixels, in place and without a host sync (yolosod_scale_boxes):
+    ``out`` [B, D, 6] fp32, ``counts`` [B] int32, ``geom`` [B, 5] fp32 = (gain, pad_x, pad_y, w0, h0) per image.
+    Rows below the image's count get ``utils.ops.scale_boxes``'s arithmetic; the padding rows stay as they are."""
+    lib = load_library()
+    if out.dim() != 3 or out.shape[2] != 6:
+        raise RuntimeError(f"scale_boxes_padded: out must be [B, D, 6], got {tuple(out.shape)}")
+    B, D = int(out.shape[0]), int(out.shape[1])
+    if tuple(counts.shape) != (B,) or tuple(geom.shape) != (B, 5):
+        raise RuntimeError(f"scale_boxes_padded: counts {tuple(counts.shape)} / geom {tuple(geom.shape)} do not match "
+                           f"{B} images")
+    _check(_launch(("scale_boxes", (B, D, 6), None), out.device, lib.yolosod_scale_boxes, _dev(out, "out"),
+                   _dev(counts, "counts", torch.int32), B, D, _dev(geom, "geom"), _stream(out.device)),
+           "scale_boxes")
+    return out
 
 
 def gemm_f32(A, B, b_kcontig, bias=None, bias_mode=0, act=0, res=None):

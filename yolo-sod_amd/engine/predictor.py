@@ -1,8 +1,10 @@
-"""Inference driver for tensor batches (the reference's predictor hot loop, minus the absent ``ultralytics/data``).
+"""Inference driver for tensor batches and for lists of raw frames (the reference's predictor hot loop; of the absent
+``ultralytics/data`` only LetterBox's geometry is restated, ``data/augment.py``).
 
 Reference flow (``engine/predictor.py:116-143, 219-304`` and ``models/yolo/detect/predict.py:23-41``):
-``preprocess`` (tensor input: ``.to(device).float()``, no /255, no letterbox) -> ``AutoBackend`` forward of the
-fused model -> ``postprocess`` = ``non_max_suppression`` + ``scale_boxes`` (same-shape input: clip to the image).
+``preprocess`` (tensor input: ``.to(device).float()``, no /255, no letterbox; list of uint8 HWC BGR frames: LetterBox,
+RGB, CHW, /255) -> ``AutoBackend`` forward of the fused model -> ``postprocess`` = ``non_max_suppression`` +
+``scale_boxes`` (same-shape tensor input: clip to the image; frames: back to each frame's pixels).
 
 MI355X additions:
 * :meth:`DetectionPredictor.predict_padded` never syncs the host: NMS returns fixed-shape ``[B, max_det, 6]``
@@ -22,6 +24,7 @@ import torch
 import torch.distributed as dist
 
 from .. import _hip
+from ..data.augment import LetterBox
 from ..utils import ops
 
 
@@ -34,23 +37,106 @@ class Detections:
     orig_shape: tuple
 
 
+class Ingested:
+    """A list of raw frames after :meth:`DetectionPredictor.preprocess`: the model's input tensor ``x``, each frame's
+    ``(h, w)`` and the device tensor ``geom`` [B, 5] = (gain, pad_x, pad_y, w0, h0) that maps boxes back."""
+
+    __slots__ = ("x", "shapes", "geom")
+
+    def __init__(self, x, shapes, geom):
+        self.x, self.shapes, self.geom = x, shapes, geom
+
+
 class DetectionPredictor:
     def __init__(self, model, conf=0.25, iou=0.7, max_det=300, classes=None, agnostic_nms=False,
-                 multi_label=False):
+                 multi_label=False, imgsz=640, rect=None):
         self.model = model
         self.conf, self.iou, self.max_det = conf, iou, max_det
         self.classes, self.agnostic, self.multi_label = classes, agnostic_nms, multi_label
         p = next(model.parameters())
         self.device, self.dtype = p.device, p.dtype
+        # list input (raw frames): the canvas, and whether same-shape batches take the minimal rectangle
+        # (None: the reference's rule, predictor.py:155-160; True / False force it)
+        self.imgsz = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
+        self.rect = rect
+        self.stride = int(max(getattr(model, "stride", torch.tensor([32.0]))))  # LetterBox's `auto` modulus
 
-    def preprocess(self, im: torch.Tensor) -> torch.Tensor:
-        """predictor.py:123-134 tensor branch: ``.to(device)``, ``.half()`` if the model is fp16 else ``.float()`` -
-        here the model's dtype (bf16 in the bf16 config)."""
+    def preprocess(self, im):
+        """predictor.py:116-134. Tensor branch: ``.to(device)``, ``.half()`` if the model is fp16 else ``.float()`` -
+        here the model's dtype (bf16 in the bf16 config); no /255, no letterbox. List branch (raw frames): see
+        :meth:`ingest`."""
+        if isinstance(im, (list, tuple)):
+            return self.ingest(im).x
         return im.to(self.device, non_blocking=True).to(self.dtype)
 
+    def ingest(self, frames) -> Ingested:
+        """predictor.py:116-134 non-tensor branch + pre_transform :145-161 for a list of uint8 HWC BGR frames (numpy
+        arrays or torch tensors, on the CPU or on the GPU, any sizes): LetterBox, BGR -> RGB, HWC -> CHW, the model's
+        dtype, / 255 - as one HIP launch on the raw bytes (``_hip.letterbox_ingest``). CPU frames go up as they are:
+        packed into one pinned buffer, one H2D copy, no host resize. Everything else here is arithmetic on shapes:
+        no host sync."""
+        if len(frames) == 0:
+            raise ValueError("DetectionPredictor: empty list of frames")
+        ts = []
+        for i, f in enumerate(frames):
+            if not isinstance(f, torch.Tensor):
+                import numpy as np
+                f = np.asarray(f)
+                if any(s < 0 for s in f.strides):
+                    f = np.ascontiguousarray(f)
+                f = torch.from_numpy(f)
+            if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
+                raise RuntimeError(f"DetectionPredictor: frame {i} must be uint8 [h, w, 3] (BGR), got {f.dtype} "
+                                   f"{tuple(f.shape)}")
+            ts.append(f)
+        shapes = [(int(t.shape[0]), int(t.shape[1])) for t in ts]
+        same = all(s == shapes[0] for s in shapes)
+        auto = same if self.rect is None else bool(self.rect)
+        if auto and not same:
+            raise ValueError("DetectionPredictor(rect=True): frames of different shapes give different canvases")
+        lb = LetterBox(self.imgsz, auto=auto, stride=self.stride)
+        geoms = [lb.geometry(s) for s in shapes]
+        canvas = geoms[0][4:]
+        # CPU frames: one pinned staging buffer (16-byte aligned slots), one copy up
+        host = [i for i, t in enumerate(ts) if t.device.type == "cpu"]
+        if host:
+            offs, total = [], 0
+            for i in host:
+                offs.append(total)
+                total += (ts[i].numel() + 15) // 16 * 16
+            stage = torch.empty(total, dtype=torch.uint8).pin_memory()
+            for i, o in zip(host, offs):
+                stage[o:o + ts[i].numel()].view(ts[i].shape).copy_(ts[i])
+            up = stage.to(self.device, non_blocking=True)
+            for i, o in zip(host, offs):
+                ts[i] = up[o:o + ts[i].numel()].view(ts[i].shape)
+        x = _hip.letterbox_ingest(ts, canvas, geoms, self.dtype, pad_value=lb.pad_value)
+        # scale_boxes' own gain / pad (ratio_pad=None, ops.py:92-105), recomputed from the two shapes as it does
+        rows = []
+        for h0, w0 in shapes:
+            gain = min(canvas[0] / h0, canvas[1] / w0)
+            rows.append([gain, round((canvas[1] - w0 * gain) / 2 - 0.1), round((canvas[0] - h0 * gain) / 2 - 0.1),
+                         w0, h0])
+        geom = torch.tensor(rows, dtype=torch.float64).to(torch.float32).pin_memory().to(self.device, non_blocking=True)
+        return Ingested(x, shapes, geom)
+
+    def _predict_ingested(self, ing: Ingested):
+        """The model, NMS and the boxes back in each frame's pixels (predict.py:23-41: scale_boxes(img.shape[2:], boxes,
+        orig_img.shape) per image) as one more launch on the padded rows."""
+        preds = self.model(ing.x)
+        y = preds[0] if isinstance(preds, (list, tuple)) else preds
+        out, counts, index = ops.non_max_suppression_padded(
+            y, self.conf, self.iou, classes=self.classes, agnostic=self.agnostic, multi_label=self.multi_label,
+            max_det=self.max_det, in_place=False)
+        _hip.scale_boxes_padded(out, counts, ing.geom)
+        return out, counts, index
+
     @torch.inference_mode()
-    def predict_padded(self, im: torch.Tensor):
-        """(out [B, max_det, 6] clipped, counts [B] int32, index [B, max_det] int32) without host sync."""
+    def predict_padded(self, im):
+        """(out [B, max_det, 6] clipped, counts [B] int32, index [B, max_det] int32) without host sync. A list of raw
+        frames (:meth:`ingest`) gives boxes in each frame's own pixels."""
+        if isinstance(im, (list, tuple)):
+            return self._predict_ingested(self.ingest(im))
         x = self.preprocess(im)
         preds = self.model(x)
         y = preds[0] if isinstance(preds, (list, tuple)) else preds
@@ -65,6 +151,8 @@ class DetectionPredictor:
     def predict_padded_guarded(self, im: torch.Tensor):
         """:meth:`predict_padded`, then the split-range guard (reads one flag word: a host sync): a batch in which an
         operand left the fp16-split kernels' range (|v| > 65504, or NaN) is redone on the exact fp32 MFMA kernels."""
+        if isinstance(im, (list, tuple)):
+            return self._predict_list_guarded(im)[:3]
         out, counts, index = self.predict_padded(im)
         if self.dtype == torch.float32 and _hip.split_range_flag(reset=True, device=self.device):
             with _hip.exact_fp32_matrix():
@@ -72,7 +160,22 @@ class DetectionPredictor:
             _hip.split_range_flag(reset=True, device=self.device)
         return out, counts, index
 
-    def __call__(self, im: torch.Tensor):
+    @torch.inference_mode()
+    def _predict_list_guarded(self, frames):
+        """The guarded step on raw frames: they are ingested once, and a redo reuses the ingested tensor."""
+        ing = self.ingest(frames)
+        out, counts, index = self._predict_ingested(ing)
+        if self.dtype == torch.float32 and _hip.split_range_flag(reset=True, device=self.device):
+            with _hip.exact_fp32_matrix():
+                out, counts, index = self._predict_ingested(ing)
+            _hip.split_range_flag(reset=True, device=self.device)
+        return out, counts, index, ing.shapes
+
+    def __call__(self, im):
+        if isinstance(im, (list, tuple)):
+            out, counts, index, shapes = self._predict_list_guarded(im)
+            n = counts.cpu().tolist()
+            return [Detections(out[i, : n[i]], index[i, : n[i]], shapes[i]) for i in range(len(n))]
         out, counts, index = self.predict_padded_guarded(im)
         n = counts.cpu().tolist()
         shape = tuple(im.shape[2:])
