@@ -207,6 +207,20 @@ int yolosod_letterbox_ingest(const int64_t* desc, int B, void* out, long out_bst
  * become (v - pad) / gain (IEEE division) clamped to [0, w0] / [0, h0]; rows >= counts[b] and columns 4, 5 are not
  * touched. D in 1..2^20. */
 int yolosod_scale_boxes(float* det, const int* counts, int B, int D, const float* geom, void* stream);
+/* Sliced inference (the project's own: the reference has no slicing), the step between the Detect head and NMS, one
+ * launch per model call. y: [n][4+nc][A] fp32, the head's output for n tiles letterboxed onto one canvas (xywh in
+ * canvas pixels, sigmoid scores). merged: [F][4+nc][S*A] fp32, one prediction tensor per frame in frame pixels, slot s
+ * at anchors [s*A, (s+1)*A). desc: device int32 [rows][16], one row per destination slot this call writes:
+ *   0 src (row of y; -1: the slot is empty, zeros are written), 1 frame, 2 slot, 3 flags (bit 0 left, 1 right, 2 top,
+ *   3 bottom tile edge interior to the frame), then fp32 bit patterns 4 gain, 5 pad_x, 6 pad_y (scale_boxes' own, of
+ *   the tile on the canvas), 7 off_x, 8 off_y (the tile's x0, y0), 9 tile_w, 10 tile_h; 11..15 unused.
+ * Per anchor, fp32 with IEEE division: b = (xy - pad) / gain, wh / gain; merged box = b + off, wh; scores are copied,
+ * or 0 when cut_margin >= 0 and the box comes within cut_margin of an interior tile edge (csrc/tile_merge.hip). Every
+ * element of a named slot is written exactly once, nothing else is touched, no atomics: deterministic. A row naming a
+ * src >= n, a frame outside [0, F) or a slot outside [0, S) writes nothing. nc in 1..64, S*A*nc < 2^32, rows in
+ * 1..65535; 16-byte accesses when A % 4 == 0 and y, merged are 16-byte aligned. */
+int yolosod_tile_merge(const float* y, int n, int nc, int A, const int32_t* desc, int rows, float* merged, int F,
+                       int S, float cut_margin, void* stream);
 
 /* Conv epilogue for the PyTorch-ROCm backbone convs (not a reference hot-path op; conv.py:37-55 + block.py:343-356
  * + Concat): out[b*out_bstride + c*HW + p] = act(y[b*y_bstride + c*HW + p] + bias[c]) (+ res[...]); act 0 id, 1 SiLU.

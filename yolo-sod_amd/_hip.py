@@ -53,6 +53,7 @@ SIGNATURES = {
     "yolosod_upsample2x": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
     "yolosod_letterbox_ingest": (_i, [_vp, _i, _vp, _l, _i, _i, _i, _i, _vp]),
     "yolosod_scale_boxes": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "yolosod_tile_merge": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _f, _vp]),
     "yolosod_stem_workspace": (_sz, [_i, _i, _i, _i]),
     "yolosod_stem_conv": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _vp, _vp, _sz, _vp]),
     "yolosod_conv1x1_thin_stats": (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _l, _i, _vp, _vp, _vp, _vp]),
@@ -1155,6 +1156,85 @@ def scale_boxes_padded(out, counts, geom):
                    _dev(counts, "counts", torch.int32), B, D, _dev(geom, "geom"), _stream(out.device)),
            "scale_boxes")
     return out
+
+
+TILE_MERGE_MAX_NC = 64  # csrc/tile_merge.hip
+
+
+def tile_merge(y, rows, merged, A, cut_margin=None):
+    """Tile outputs into per-frame prediction tensors in frame pixels, one launch (yolosod_tile_merge): ``y``
+    [n, 4+nc, A] fp32 is the Detect output of one model call on n tiles (canvas pixels), ``merged`` [F, 4+nc, S*A] fp32
+    the batch's NMS input; ``rows`` names the destination slots this call writes, one
+    ``(src, frame, slot, gain, pad_x, pad_y, off_x, off_y, tile_w, tile_h, (left, right, top, bottom))`` each
+    (``SlicePlan.merge_rows``): ``src`` a row of y, or -1 for an empty slot (zeros); gain / pad as ``scale_boxes``
+    computes them for the tile on the canvas; ``off`` the tile's x0, y0; the last entry says which tile edges are
+    interior to the frame. ``cut_margin``: scores of boxes that come within this many tile pixels of an interior edge
+    are zeroed (None or negative: off). Returns ``merged``.
+
+    The descriptor is built here and goes up as one pinned non-blocking copy; everything the kernel relies on is
+    checked here first: nothing is launched on arguments that fail."""
+    import numpy as np
+    lib = load_library()
+    for t, name in ((y, "y"), (merged, "merged")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"tile_merge: {name}: expected a tensor")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"tile_merge: {name}: HIP kernel requires a GPU tensor (got device {t.device}); "
+                               "no CPU fallback")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"tile_merge: {name}: expected float32, got {t.dtype}")
+        if t.dim() != 3:
+            raise RuntimeError(f"tile_merge: {name}: expected 3 dimensions, got shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"tile_merge: {name}: expected a contiguous tensor")
+    if merged.device != y.device:
+        raise RuntimeError(f"tile_merge: y on {y.device}, merged on {merged.device}")
+    n, no, A = int(y.shape[0]), int(y.shape[1]), int(A)
+    nc = no - 4
+    if A < 1 or int(y.shape[2]) != A:
+        raise RuntimeError(f"tile_merge: y has {int(y.shape[2])} anchors, A = {A}")
+    if n < 1 or not 1 <= nc <= TILE_MERGE_MAX_NC:
+        raise RuntimeError(f"tile_merge: y {tuple(y.shape)} unsupported (n >= 1, 1..{TILE_MERGE_MAX_NC} classes)")
+    F, SA = int(merged.shape[0]), int(merged.shape[2])
+    if F < 1 or int(merged.shape[1]) != no or SA < A or SA % A:
+        raise RuntimeError(f"tile_merge: merged {tuple(merged.shape)} is not [F, {no}, S * {A}]")
+    S = SA // A
+    if S * A * nc >= 1 << 32:
+        raise RuntimeError(f"tile_merge: S * A * nc = {S} * {A} * {nc} >= 2^32")
+    rows = list(rows)
+    if not 1 <= len(rows) <= 65535:
+        raise RuntimeError(f"tile_merge: {len(rows)} descriptor rows (1..65535)")
+    desc = np.zeros((len(rows), 16), dtype=np.int32)
+    fl = desc.view(np.float32)
+    named = set()
+    for i, r in enumerate(rows):
+        if len(r) != 11 or len(r[10]) != 4:
+            raise RuntimeError(f"tile_merge: row {i}: expected (src, frame, slot, gain, pad_x, pad_y, off_x, off_y, "
+                               "tile_w, tile_h, (left, right, top, bottom))")
+        src, frame, slot = int(r[0]), int(r[1]), int(r[2])
+        if not -1 <= src < n:
+            raise RuntimeError(f"tile_merge: row {i}: src {src} outside [-1, {n})")
+        if not 0 <= frame < F:
+            raise RuntimeError(f"tile_merge: row {i}: frame {frame} outside [0, {F})")
+        if not 0 <= slot < S:
+            raise RuntimeError(f"tile_merge: row {i}: slot {slot} outside [0, {S})")
+        if (frame, slot) in named:
+            raise RuntimeError(f"tile_merge: row {i}: slot {slot} of frame {frame} is named twice")
+        named.add((frame, slot))
+        gain = float(r[3])
+        if src >= 0 and not (gain > 0.0 and gain < float("inf")):
+            raise RuntimeError(f"tile_merge: row {i}: gain {gain}")
+        desc[i, :3] = (src, frame, slot)
+        desc[i, 3] = sum(1 << k for k in range(4) if r[10][k])
+        fl[i, 4:11] = [float(v) for v in r[3:10]]
+    cm = -1.0 if cut_margin is None else float(cut_margin)
+    if cm != cm:
+        raise RuntimeError("tile_merge: cut_margin is NaN")
+    dev = y.device
+    d = torch.from_numpy(desc).pin_memory().to(dev, non_blocking=True)
+    _check(_launch(("tile_merge", (n, no, A), (F, S)), dev, lib.yolosod_tile_merge, y.data_ptr(), n, nc, A,
+                   d.data_ptr(), len(rows), merged.data_ptr(), F, S, cm, _stream(dev)), "tile_merge")
+    return merged
 
 
 def gemm_f32(A, B, b_kcontig, bias=None, bias_mode=0, act=0, res=None):

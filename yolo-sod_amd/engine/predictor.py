@@ -25,6 +25,7 @@ import torch.distributed as dist
 
 from .. import _hip
 from ..data.augment import LetterBox
+from ..data.slicing import SlicePlan
 from ..utils import ops
 
 
@@ -45,6 +46,39 @@ class Ingested:
 
     def __init__(self, x, shapes, geom):
         self.x, self.shapes, self.geom = x, shapes, geom
+
+
+def frames_to_device(frames, device, who="DetectionPredictor"):
+    """A list of uint8 HWC BGR frames (numpy arrays or torch tensors, on the CPU or on the GPU, any sizes) as a list of
+    uint8 [h, w, 3] tensors on the GPU. CPU frames go up as they are: packed into one pinned staging buffer (16-byte
+    aligned slots), one H2D copy, no host sync; GPU frames pass through untouched."""
+    if len(frames) == 0:
+        raise ValueError(f"{who}: empty list of frames")
+    ts = []
+    for i, f in enumerate(frames):
+        if not isinstance(f, torch.Tensor):
+            import numpy as np
+            f = np.asarray(f)
+            if any(s < 0 for s in f.strides):
+                f = np.ascontiguousarray(f)
+            f = torch.from_numpy(f)
+        if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
+            raise RuntimeError(f"{who}: frame {i} must be uint8 [h, w, 3] (BGR), got {f.dtype} "
+                               f"{tuple(f.shape)}")
+        ts.append(f)
+    host = [i for i, t in enumerate(ts) if t.device.type == "cpu"]
+    if host:
+        offs, total = [], 0
+        for i in host:
+            offs.append(total)
+            total += (ts[i].numel() + 15) // 16 * 16
+        stage = torch.empty(total, dtype=torch.uint8).pin_memory()
+        for i, o in zip(host, offs):
+            stage[o:o + ts[i].numel()].view(ts[i].shape).copy_(ts[i])
+        up = stage.to(device, non_blocking=True)
+        for i, o in zip(host, offs):
+            ts[i] = up[o:o + ts[i].numel()].view(ts[i].shape)
+    return ts
 
 
 class DetectionPredictor:
@@ -75,20 +109,7 @@ class DetectionPredictor:
         dtype, / 255 - as one HIP launch on the raw bytes (``_hip.letterbox_ingest``). CPU frames go up as they are:
         packed into one pinned buffer, one H2D copy, no host resize. Everything else here is arithmetic on shapes:
         no host sync."""
-        if len(frames) == 0:
-            raise ValueError("DetectionPredictor: empty list of frames")
-        ts = []
-        for i, f in enumerate(frames):
-            if not isinstance(f, torch.Tensor):
-                import numpy as np
-                f = np.asarray(f)
-                if any(s < 0 for s in f.strides):
-                    f = np.ascontiguousarray(f)
-                f = torch.from_numpy(f)
-            if f.dtype != torch.uint8 or f.dim() != 3 or f.shape[2] != 3:
-                raise RuntimeError(f"DetectionPredictor: frame {i} must be uint8 [h, w, 3] (BGR), got {f.dtype} "
-                                   f"{tuple(f.shape)}")
-            ts.append(f)
+        ts = frames_to_device(frames, self.device, "DetectionPredictor")
         shapes = [(int(t.shape[0]), int(t.shape[1])) for t in ts]
         same = all(s == shapes[0] for s in shapes)
         auto = same if self.rect is None else bool(self.rect)
@@ -97,19 +118,6 @@ class DetectionPredictor:
         lb = LetterBox(self.imgsz, auto=auto, stride=self.stride)
         geoms = [lb.geometry(s) for s in shapes]
         canvas = geoms[0][4:]
-        # CPU frames: one pinned staging buffer (16-byte aligned slots), one copy up
-        host = [i for i, t in enumerate(ts) if t.device.type == "cpu"]
-        if host:
-            offs, total = [], 0
-            for i in host:
-                offs.append(total)
-                total += (ts[i].numel() + 15) // 16 * 16
-            stage = torch.empty(total, dtype=torch.uint8).pin_memory()
-            for i, o in zip(host, offs):
-                stage[o:o + ts[i].numel()].view(ts[i].shape).copy_(ts[i])
-            up = stage.to(self.device, non_blocking=True)
-            for i, o in zip(host, offs):
-                ts[i] = up[o:o + ts[i].numel()].view(ts[i].shape)
         x = _hip.letterbox_ingest(ts, canvas, geoms, self.dtype, pad_value=lb.pad_value)
         # scale_boxes' own gain / pad (ratio_pad=None, ops.py:92-105), recomputed from the two shapes as it does
         rows = []
@@ -180,6 +188,133 @@ class DetectionPredictor:
         n = counts.cpu().tolist()
         shape = tuple(im.shape[2:])
         return [Detections(out[i, : n[i]], index[i, : n[i]], shape) for i in range(len(n))]
+
+
+class SlicedPredictor:
+    """Sliced inference for frames much larger than the canvas (the project's own; the reference has none): every frame
+    is cut into overlapping ``slice`` tiles at native resolution (``data/slicing.py``), the model runs on the tiles and,
+    with ``full_frame``, on the whole frame too, and all candidates of a frame meet in ONE NMS in frame pixels.
+
+    Takes a list of uint8 HWC BGR frames (numpy arrays, CPU or GPU tensors, any sizes). Stages, each a method so that a
+    test or a validator can check it on the same tensors: :meth:`plan` (host arithmetic) -> :meth:`forward_tiles`
+    (tiles are views of the device frames, letterboxed onto the one canvas by ``_hip.letterbox_ingest`` straight from
+    the frame's memory, ``batch`` tiles per model call, tiles of different frames share a call) -> :meth:`merge`
+    (``_hip.tile_merge`` per call into merged [F, 4+nc, S*A], frame pixels) -> :meth:`postprocess` (NMS on merged,
+    clip to the frame). ``index`` of a detection is ``slot * A + anchor``; ``plan.slot(frame, slot)`` is its tile.
+
+    ``cut_margin`` (tile pixels; None: off): a candidate whose box comes within it of a tile edge that is interior to
+    the frame is dropped before NMS - the tile saw the object truncated, a neighbouring tile or the whole-frame slot
+    sees it whole. ``merged`` takes F * (4+nc) * S * A * 4 bytes."""
+
+    def __init__(self, model, slice=640, overlap=0.2, full_frame=True, cut_margin=None, batch=32, conf=0.25, iou=0.7,
+                 max_det=300, classes=None, agnostic_nms=False, multi_label=False, imgsz=640):
+        self.model = model
+        self.slice, self.overlap, self.full_frame = slice, overlap, bool(full_frame)
+        self.cut_margin = None if cut_margin is None else float(cut_margin)
+        self.batch = int(batch)
+        if self.batch < 1:
+            raise ValueError(f"SlicedPredictor: batch={batch}")
+        self.conf, self.iou, self.max_det = conf, iou, max_det
+        self.classes, self.agnostic, self.multi_label = classes, agnostic_nms, multi_label
+        p = next(model.parameters())
+        self.device, self.dtype = p.device, p.dtype
+        self.imgsz = (imgsz, imgsz) if isinstance(imgsz, int) else tuple(imgsz)
+        self.stride = int(max(getattr(model, "stride", torch.tensor([32.0]))))
+
+    def plan(self, shapes) -> SlicePlan:
+        """The slots of frames of these ``(h, w)`` shapes."""
+        return SlicePlan(shapes, self.slice, self.overlap, self.full_frame, self.imgsz, self.stride)
+
+    def _views(self, ts, plan, lo, hi):
+        views = []
+        for f, k in plan.order[lo:hi]:
+            y0, x0, y1, x1 = plan.slots[f][k].rect
+            views.append(ts[f][y0:y1, x0:x1])
+        return views
+
+    def ingest_tiles(self, frames, plan, lo=0, hi=None):
+        """The model's input for tiles ``plan.order[lo:hi]``: [hi - lo, 3, *canvas], one launch on views of the frames."""
+        ts = frames_to_device(frames, self.device, "SlicedPredictor")
+        hi = len(plan) if hi is None else hi
+        geoms = [plan.slots[f][k].geometry for f, k in plan.order[lo:hi]]
+        return _hip.letterbox_ingest(self._views(ts, plan, lo, hi), plan.canvas, geoms, self.dtype,
+                                     pad_value=plan.pad_value)
+
+    @torch.inference_mode()
+    def forward_tiles(self, frames, plan):
+        """The Detect outputs [n_i, 4+nc, A] (fp32, canvas pixels) of the model calls, ``batch`` tiles at most each, in
+        ``plan.order``. CPU frames go up once."""
+        ts = frames_to_device(frames, self.device, "SlicedPredictor")
+        if [tuple(t.shape[:2]) for t in ts] != plan.shapes:
+            raise ValueError("SlicedPredictor: the plan was made for other frame shapes")
+        ys = []
+        for lo, hi in plan.chunks(self.batch):
+            preds = self.model(self.ingest_tiles(ts, plan, lo, hi))
+            ys.append(preds[0] if isinstance(preds, (list, tuple)) else preds)
+        return ys
+
+    def merge(self, y_chunks, plan):
+        """merged [F, 4+nc, S*A] in frame pixels from the model calls' outputs (any grouping of ``plan.order`` into
+        consecutive calls): one ``_hip.tile_merge`` launch per call; every (frame, slot) is written exactly once."""
+        if not y_chunks or sum(int(y.shape[0]) for y in y_chunks) != len(plan):
+            raise ValueError(f"SlicedPredictor.merge: the chunks hold {sum(int(y.shape[0]) for y in y_chunks)} tiles, "
+                             f"the plan {len(plan)}")
+        y0 = y_chunks[0]
+        if not isinstance(y0, torch.Tensor) or y0.device.type != "cuda":
+            raise RuntimeError("SlicedPredictor.merge: HIP kernel requires GPU tensors; no CPU fallback")
+        no, A = int(y0.shape[1]), int(y0.shape[2])
+        merged = torch.empty((len(plan.shapes), no, plan.S * A), dtype=torch.float32, device=y0.device)
+        lo = 0
+        for y in y_chunks:
+            hi = lo + int(y.shape[0])
+            _hip.tile_merge(y, plan.merge_rows(lo, hi), merged, A, self.cut_margin)
+            lo = hi
+        return merged
+
+    def postprocess(self, merged, plan):
+        """One NMS per frame over all its slots, boxes clipped to the frame: (out [F, max_det, 6], counts [F],
+        index [F, max_det] = slot * A + anchor)."""
+        out, counts, index = ops.non_max_suppression_padded(
+            merged, self.conf, self.iou, classes=self.classes, agnostic=self.agnostic, multi_label=self.multi_label,
+            max_det=self.max_det, max_wh=max(7680, max(max(s) for s in plan.shapes)), in_place=False)
+        geom = torch.tensor([[1.0, 0.0, 0.0, w, h] for h, w in plan.shapes], dtype=torch.float32)
+        _hip.scale_boxes_padded(out, counts, geom.pin_memory().to(out.device, non_blocking=True))
+        return out, counts, index
+
+    @torch.inference_mode()
+    def _predict(self, ts, plan):
+        return self.postprocess(self.merge(self.forward_tiles(ts, plan), plan), plan)
+
+    def _start(self, frames):
+        if not isinstance(frames, (list, tuple)):
+            raise TypeError("SlicedPredictor: expected a list of uint8 [h, w, 3] frames")
+        ts = frames_to_device(frames, self.device, "SlicedPredictor")
+        return ts, self.plan([t.shape[:2] for t in ts])
+
+    def predict_padded(self, frames):
+        """(out [F, max_det, 6] in each frame's pixels, counts [F] int32, index [F, max_det] int32), no host sync."""
+        ts, plan = self._start(frames)
+        return self._predict(ts, plan)
+
+    def _predict_guarded(self, frames):
+        ts, plan = self._start(frames)
+        res = self._predict(ts, plan)
+        if self.dtype == torch.float32 and _hip.split_range_flag(reset=True, device=self.device):
+            with _hip.exact_fp32_matrix():
+                res = self._predict(ts, plan)
+            _hip.split_range_flag(reset=True, device=self.device)
+        return res, plan
+
+    def predict_padded_guarded(self, frames):
+        """:meth:`predict_padded`, then the split-range guard as ``DetectionPredictor.predict_padded_guarded``: the flag
+        is read once (a host sync) and a batch that left the fp16-split kernels' range is redone on the exact fp32
+        kernels (the frames are not uploaded again)."""
+        return self._predict_guarded(frames)[0]
+
+    def __call__(self, frames):
+        (out, counts, index), plan = self._predict_guarded(frames)
+        n = counts.cpu().tolist()
+        return [Detections(out[i, : n[i]], index[i, : n[i]], plan.shapes[i]) for i in range(len(n))]
 
 
 def shard_bounds(n: int, rank: int, world: int):
