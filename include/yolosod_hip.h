@@ -375,6 +375,15 @@ int yolosod_conv1x1x2_silu_cat(const float* x, long x_bstride, const float* x2, 
 /* Timing hook: ablation variants of the stride-2 conv kernel at Cout 64 with a channel gate (csrc/conv3x3s2.hip; WRONG
  * results for abl != 0 - scripts/bench_conv3x3s2.py only). Returns the previous value. */
 int yolosod_debug_set_conv3x3s2_abl(int abl);
+/* Test / measurement hook: the form the tiled stride-2 conv kernel (csrc/conv3x3s2.hip) takes. form = geometry +
+ * 4 * groups: geometry 0 automatic, 1 the 32 x 2 output tile of 16 x 1 pixel blocks, 2 the 40 x 2 tile of 8 x 2 blocks,
+ * 3 the 20 x 4 tile of 4 x 4 blocks; groups 0 automatic, 1 128-channel output groups, 2 64-channel groups (Cout 64 always
+ * runs 64-channel groups). Every form gives bit-identical results. Values outside [0, 12) are ignored. Returns the
+ * previous value. */
+int yolosod_debug_set_conv3x3s2_form(int form);
+/* The form (same encoding, no field 0) a [B][*][H][W] -> cout launch of yolosod_conv3x3s2_silu* runs in under the
+ * current setting; 0 for shapes the kernel does not take (output width not a multiple of 4, unsupported cout). */
+int yolosod_debug_conv3x3s2_form(int B, int cout, int H, int W);
 /* Timing hook: ablation variants of the 3x3 conv kernel (csrc/conv3x3.hip; WRONG results for any abl != 0 and
  * != 16 - scripts/bench_conv3x3.py only). Returns the previous value. */
 int yolosod_debug_set_conv3x3_abl(int abl);

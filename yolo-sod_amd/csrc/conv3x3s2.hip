@@ -460,12 +460,60 @@ __global__ __launch_bounds__(NTk, 512 / NTk) void conv3x3s2_rw_kernel(Args p) {
 // general kernel's streamed weights (one tap ahead, the next (tile, chunk)'s input spread over the taps behind them;
 // two per CU at Cout 128, whose 8 accumulator tiles per wave need more than 168 registers)
 // with the register-weight kernel's unclamped per-image buffer addressing; wave w computes channel blocks
-// CBW w .. + CBW - 1 (CBW = NCB / 4) for all four pixel blocks of the tile (rows 0, 1 x two 16-column blocks).
-template <int NCB, int GATE>
-__global__ __launch_bounds__(256, NCB == 8 ? 2 : 3) void conv3x3s2_t2_kernel(Args p) {
-  constexpr int THk = 2, NTk = 256, HRk = 2 * THk + 1, NPXk = HRk * HC, PLk = NPXk * PS, NQUADk = NPXk * 8;
-  constexpr int NITk = (NQUADk + NTk - 1) / NTk, NGPk = (NPXk + NTk - 1) / NTk, CBW = NCB / 4;
+// CBW w .. + CBW - 1 (CBW = NCB / 4) for every pixel block of the tile.
+//
+// Geometry G (chosen per launch, s2_form): a lane holds output pixels 4 g .. + 3 of a 16-pixel block, so a block may
+// be 16 x 1, 8 x 2 or 4 x 4 output pixels (BW x BH) with the same 16-byte stores; a tile is TBX x TBY blocks and every
+// wave computes all of them. The order of an output element's additions (chunk -> tap -> product) does not depend on
+// G or NCB: every form is bit-identical.
+//   G 0: 16 x 1 blocks, 2 x 2: the 32 x 2 tile, input halo 65 x 5 (40-wide outputs: 62.5 % of the MFMAs useful)
+//   G 1:  8 x 2 blocks, 5 x 1: a 40 x 2 tile, halo 81 x 5 (40-wide outputs covered exactly)
+//   G 2:  4 x 4 blocks, 5 x 1: a 20 x 4 tile, halo 41 x 9 (20-wide outputs covered exactly)
+// RS: the LDS row stride in pixels. A ds_read_b128 is served in four groups of 16 lanes ({0-3, 12-15, 20-27}, {4-11,
+// 16-19, 28-31}, + 32), conflict-free when the group's sixteen 16-byte slots differ mod 16; with 5 slots per pixel
+// (PS = 40) and stride-2 pixel reads a block row must start at slot 0 (mod 16) of the previous one's for 8 x 2 and at
+// slot 8 for 4 x 4: RS = 0 (mod 8) >= 81 -> 88, RS = 4 (mod 8) >= 41 -> 44 (tests/test_conv3x3s2_lds_banks.py).
+template <int G>
+struct Geo;
+template <>
+struct Geo<0> {
+  static constexpr int BW = 16, TBX = 2, TBY = 2, RS = 65;
+};
+template <>
+struct Geo<1> {
+  static constexpr int BW = 8, TBX = 5, TBY = 1, RS = 88;
+};
+template <>
+struct Geo<2> {
+  static constexpr int BW = 4, TBX = 5, TBY = 1, RS = 44;
+};
+template <int G>
+struct GeoD : Geo<G> {
+  using B = Geo<G>;
+  static constexpr int BH = 16 / B::BW, NBLK = B::TBX * B::TBY;
+  static constexpr int TW = B::TBX * B::BW, TH = B::TBY * BH, HC = 2 * TW + 1, HR = 2 * TH + 1, NPX = HR * HC;
+  static constexpr int PL = HR * B::RS * PS;  // plane (halves)
+  static constexpr int NQUAD = NPX * 8, NIT = (NQUAD + 255) / 256;
+  static_assert(B::RS >= HC && NIT <= 32 && HC < 256 && HR < 256, "conv3x3s2 geometry");
+};
+
+// 1: the pixel fragments are read one (tap, pixel block) step ahead of their MFMAs (3 - 5 % per launch on the 5-block
+// forms); 0: right before them (the A/B arm of DESIGN §18; its both-gates 40 x 2 instance spills 12 bytes)
+#ifndef YS_S2_READ_AHEAD
+#define YS_S2_READ_AHEAD 1
+#endif
+
+template <int NCB, int GATE, int G>
+__global__ __launch_bounds__(256, (NCB == 8 || G != 0) ? 2 : 3) void conv3x3s2_t2_kernel(Args p) {
+  using Ge = GeoD<G>;
+  constexpr int BW = Ge::BW, BH = Ge::BH, TBX = Ge::TBX, NBLK = Ge::NBLK, RS = Ge::RS;
+  constexpr int THk = Ge::TH, TW = Ge::TW, HC = Ge::HC;  // this geometry's, not the 4 x 32 tile's of the file scope
+  constexpr int NTk = 256, HRk = Ge::HR, NPXk = Ge::NPX, PLk = Ge::PL, NQUADk = Ge::NQUAD;
+  constexpr int NITk = Ge::NIT, NGPk = (NPXk + NTk - 1) / NTk, CBW = NCB / 4;
   static_assert(NCB == 4 || NCB == 8, "Cout 64 or 128");
+  // with the read-ahead built in, the three-per-CU instances still keep the fragment reads at their use: the
+  // 168-register budget has no room for the fragments in flight (the channel-gated one spilled)
+  constexpr bool RA = YS_S2_READ_AHEAD != 0 && !(NCB == 4 && G == 0);
   __shared__ __attribute__((aligned(16))) h16_t Pl[2 * PLk];
   __shared__ __attribute__((aligned(16))) float gcs[32];
   __shared__ float gps[(GATE & 2) ? NPXk : 1];
@@ -565,12 +613,14 @@ __global__ __launch_bounds__(256, NCB == 8 ? 2 : 3) void conv3x3s2_t2_kernel(Arg
     const int st = __builtin_amdgcn_readfirstlane((((t * nq + q) * p.ncb_all + cb) * 2 + pl) * 1024);
     return __builtin_bit_cast(f16x8_t, __builtin_amdgcn_raw_buffer_load_b128(rw, (unsigned)(lane * 16), st, 0));
   };
-  int bpx[4];
+  // pixel block k = (k / TBX, k % TBX) of the tile; the lane's pixel l15 of it = (l15 / BW, l15 % BW): its halo pixel
+  // at tap (0, 0) in the plane
+  int bpx[NBLK];
 #pragma unroll
-  for (int k = 0; k < 4; ++k) bpx[k] = 2 * (k >> 1) * HC + 2 * ((k & 1) * 16 + l15);
-  f32x4 acc[4][CBW];
+  for (int k = 0; k < NBLK; ++k) bpx[k] = 2 * ((k / TBX) * BH + l15 / BW) * RS + 2 * ((k % TBX) * BW + l15 % BW);
+  f32x4 acc[NBLK][CBW];
 #pragma unroll
-  for (int k = 0; k < 4; ++k)
+  for (int k = 0; k < NBLK; ++k)
 #pragma unroll
     for (int u = 0; u < CBW; ++u) acc[k][u] = f32x4{0.f, 0.f, 0.f, 0.f};
   const int nw = __builtin_amdgcn_readfirstlane(p.Wo);
@@ -606,7 +656,8 @@ __global__ __launch_bounds__(256, NCB == 8 ? 2 : 3) void conv3x3s2_t2_kernel(Arg
         uint2 hh, ll;
         split4x(v, hh, ll);
         rng = range_acc(rng, v);
-        h16_t* d = Pl + px * PS + 4 * quad;
+        const int pxl = RS == HC ? px : ((pk[i] >> 8) & 255) * RS + (pk[i] & 255);  // the pixel's place in the plane
+        h16_t* d = Pl + pxl * PS + 4 * quad;
         *reinterpret_cast<uint2*>(d) = hh;
         *reinterpret_cast<uint2*>(d + PLk) = ll;
       }
@@ -620,6 +671,16 @@ __global__ __launch_bounds__(256, NCB == 8 ? 2 : 3) void conv3x3s2_t2_kernel(Arg
       wa[u][0] = wfrag(0, r.q, cb0 + u, 0);
       wa[u][1] = wfrag(0, r.q, cb0 + u, 1);
     }
+    // RA: pixel fragments one (tap, pixel block) step ahead of their MFMAs (across taps too), and group barriers that
+    // keep each step's two LDS reads ahead of the previous step's MFMAs (as conv3x3_p_kernel); otherwise each block's
+    // reads sit right before its MFMAs
+    auto rd = [&](int t, int k, f16x8_t& h, f16x8_t& l) __attribute__((always_inline)) {
+      const h16_t* src = Pl + (bpx[k] + (t / 3) * RS + (t % 3)) * PS + 8 * g;
+      h = *reinterpret_cast<const f16x8_t*>(src);
+      l = *reinterpret_cast<const f16x8_t*>(src + PLk);
+    };
+    f16x8_t nh, nl;
+    if constexpr (RA) rd(0, 0, nh, nl);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
@@ -632,17 +693,28 @@ __global__ __launch_bounds__(256, NCB == 8 ? 2 : 3) void conv3x3s2_t2_kernel(Arg
       if (t < 8) load_part(cur, PER_TAP * t, min(PER_TAP * t + PER_TAP, NLD));
       else load_gates(cur);
       __builtin_amdgcn_sched_barrier(0);
-      const int toff = (t / 3) * HC + (t % 3);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const h16_t* src = Pl + (bpx[k] + toff) * PS + 8 * g;
-        const f16x8_t xh = *reinterpret_cast<const f16x8_t*>(src);
-        const f16x8_t xl = *reinterpret_cast<const f16x8_t*>(src + PLk);
+      for (int k = 0; k < NBLK; ++k) {
+        f16x8_t xh, xl;
+        if constexpr (RA) {
+          xh = nh, xl = nl;
+          if (k < NBLK - 1) rd(t, k + 1, nh, nl);
+          else if (t < 8) rd(t + 1, 0, nh, nl);
+        } else {
+          rd(t, k, xh, xl);
+        }
 #pragma unroll
         for (int u = 0; u < CBW; ++u) {
           f32x4 c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wa[u][1], acc[k][u], 0, 0, 0);
           c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wa[u][0], c, 0, 0, 0);
           acc[k][u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wa[u][0], c, 0, 0, 0);
+        }
+      }
+      if constexpr (RA) {
+#pragma unroll
+        for (int k = 0; k < NBLK; ++k) {
+          if (k < NBLK - 1 || t < 8) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read
+          __builtin_amdgcn_sched_group_barrier(0x008, 3 * CBW, 0);                       // MFMA
         }
       }
 #pragma unroll
@@ -655,16 +727,18 @@ __global__ __launch_bounds__(256, NCB == 8 ? 2 : 3) void conv3x3s2_t2_kernel(Arg
       float bo[CBW];
 #pragma unroll
       for (int u = 0; u < CBW; ++u) bo[u] = bsh[16 * (cb0 + u) + l15];
-      f32x4 v[4][CBW];
+      f32x4 v[NBLK][CBW];
 #pragma unroll
-      for (int k = 0; k < 4; ++k)
+      for (int k = 0; k < NBLK; ++k)
 #pragma unroll
         for (int u = 0; u < CBW; ++u)
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[k][u][e] = silu_fast_(acc[k][u][e] * (1.0f / WSC) + bo[u]);
+      // lane (g, l15) of pixel block k holds channel l15 of its block, pixels 4 g .. + 3 of the block: row (4 g) / BW,
+      // columns (4 g) % BW .. + 3
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int oy = r.ty * THk + (k >> 1), ox = r.tx * TW + (k & 1) * 16 + 4 * g;
+      for (int k = 0; k < NBLK; ++k) {
+        const int oy = r.ty * THk + (k / TBX) * BH + (4 * g) / BW, ox = r.tx * TW + (k % TBX) * BW + (4 * g) % BW;
 #pragma unroll
         for (int u = 0; u < CBW; ++u) {
           const int o = 16 * (cb0 + u) + l15;
@@ -733,6 +807,52 @@ YS_EXPORT size_t yolosod_conv3x3s2_prep_bytes(int cin, int cout) {
   s.take<h16_t>((size_t)2 * cout * cin * 9);
   s.take<unsigned>(1);
   return s.off;
+}
+
+// Forced form of the tiled kernel (tests / per-shape measurements compare forms; the automatic choice is the
+// product): form = geometry + 4 groups; geometry 0 automatic, 1 the 32 x 2 tile, 2 the 40 x 2 tile of 8 x 2 blocks,
+// 3 the 20 x 4 tile of 4 x 4 blocks; groups 0 automatic, 1 128-channel output groups, 2 64-channel groups (Cout 64
+// has 64-channel groups only, whatever is forced). Every geometry takes every shape. Returns the previous value.
+static int g_s2_form = 0;
+YS_EXPORT int yolosod_debug_set_conv3x3s2_form(int form) {
+  const int old = g_s2_form;
+  if (form >= 0 && form < 12) g_s2_form = form;
+  return old;
+}
+
+static const int S2_GEO_TW[3] = {c3s2::GeoD<0>::TW, c3s2::GeoD<1>::TW, c3s2::GeoD<2>::TW};
+static const int S2_GEO_TH[3] = {c3s2::GeoD<0>::TH, c3s2::GeoD<1>::TH, c3s2::GeoD<2>::TH};
+
+// The geometry with the fewest tiles for an Ho x Wo output (the 40 x 2 and 20 x 4 tiles carry 1.25 times a 32 x 2
+// tile's MFMA work, useful or not: compared in blocks); the 32 x 2 tile on a tie and for every output above 40 x 40
+// (a store's 16 lanes cover 64 contiguous bytes per channel there, 32 or 16 in the other forms).
+static int s2_pick_geo(int Ho, int Wo) {
+  if ((long)Ho * Wo > 1600) return 0;
+  static const int nblk[3] = {c3s2::GeoD<0>::NBLK, c3s2::GeoD<1>::NBLK, c3s2::GeoD<2>::NBLK};
+  int best = 0;
+  long nbest = 0;
+  for (int g = 0; g < 3; ++g) {
+    const long n = (long)((Wo + S2_GEO_TW[g] - 1) / S2_GEO_TW[g]) * ((Ho + S2_GEO_TH[g] - 1) / S2_GEO_TH[g]) * nblk[g];
+    if (g == 0 || n < nbest) best = g, nbest = n;
+  }
+  return best;
+}
+
+// The resolved form (geometry 1 .. 3 + 4 * groups 1 .. 2) of a launch: the forced fields of g_s2_form, the automatic
+// choice for the others. 128-channel groups whenever Cout has them (64-channel groups halve the MFMAs per LDS read
+// and per weight fragment; measured slower on every model shape).
+static int s2_form(int B, int cout, int Ho, int Wo) {
+  const int fgeo = g_s2_form & 3, fgrp = (g_s2_form >> 2) & 3;
+  const int geo = fgeo ? fgeo - 1 : s2_pick_geo(Ho, Wo);
+  const bool g64 = cout == 64 || fgrp == 2;
+  return geo + 1 + 4 * (g64 ? 2 : 1);
+}
+
+// The form (as yolosod_debug_set_conv3x3s2_form encodes it, no field 0) the tiled kernel runs a [B][*][H][W] -> cout
+// launch in under the current setting; 0 for shapes it does not take.
+YS_EXPORT int yolosod_debug_conv3x3s2_form(int B, int cout, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0 || ((W + 1) / 2) % 4 || !(cout == 64 || (cout % 128 == 0 && cout <= 512))) return 0;
+  return s2_form(B, cout, (H + 1) / 2, (W + 1) / 2);
 }
 
 static bool s2_carve(void* buf, size_t bytes, int cin, int cout, h16_t** wp, unsigned** flag) {
@@ -822,28 +942,32 @@ YS_EXPORT int yolosod_conv3x3s2_silu_out(const float* x, float* y, long y_bstrid
     else if (gate == 2) S2RW_LAUNCH(2, 0);
     else S2RW_LAUNCH(3, 0);
 #undef S2RW_LAUNCH
-  } else if (g_s2_abl < 100 || cout > 128) {  // 2-row tiles, 3 (Cout 64) / 2 workgroups per CU
+  } else if (g_s2_abl < 100 || cout > 128) {  // the tiled kernel in the form s2_form picks
+    const int form = s2_form(B, cout, Ho, Wo);
+    const int geo = (form & 3) - 1;
+    const bool g64 = (form >> 2) == 2;
     c3s2::Args a2 = a;
-    a2.tiles_y = (Ho + 1) / 2;
-    const long nt2 = (long)B * a2.tiles_y * tx * (cout == 64 ? 1 : cout / 128);  // work items: (tile, group)
-    a2.ntiles = (int)((long)B * a2.tiles_y * tx);
-    long g2 = (cout == 64 ? 3L : 2L) * s2_cu_count();
-    g2 = g2 < ((nt2 + 7) / 8) * 8 ? g2 : ((nt2 + 7) / 8) * 8;
+    a2.tiles_x = (Wo + S2_GEO_TW[geo] - 1) / S2_GEO_TW[geo];
+    a2.tiles_y = (Ho + S2_GEO_TH[geo] - 1) / S2_GEO_TH[geo];
+    const long nt2 = (long)B * a2.tiles_y * a2.tiles_x;
+    const long nitems = nt2 * (g64 ? cout / 64 : cout / 128);  // work items: (tile, group)
+    YS_CHECK_ARG(nitems < (1L << 30), "conv3x3s2: too many tiles");
+    a2.ntiles = (int)nt2;
+    // workgroups per CU of the instance: three for 64-channel groups on the 32 x 2 tile, two otherwise
+    long g2 = (g64 && geo == 0 ? 3L : 2L) * s2_cu_count();
+    g2 = g2 < ((nitems + 7) / 8) * 8 ? g2 : ((nitems + 7) / 8) * 8;
     g2 = (g2 + 7) / 8 * 8;
-#define S2T2_LAUNCH(NCB_, G_) \
-  hipLaunchKernelGGL((c3s2::conv3x3s2_t2_kernel<NCB_, G_>), dim3((unsigned)g2), dim3(256), 0, st, a2)
-    if (cout == 64) {
-      if (gate == 0) S2T2_LAUNCH(4, 0);
-      else if (gate == 1) S2T2_LAUNCH(4, 1);
-      else if (gate == 2) S2T2_LAUNCH(4, 2);
-      else S2T2_LAUNCH(4, 3);
-    } else {
-      if (gate == 0) S2T2_LAUNCH(8, 0);
-      else if (gate == 1) S2T2_LAUNCH(8, 1);
-      else if (gate == 2) S2T2_LAUNCH(8, 2);
-      else S2T2_LAUNCH(8, 3);
-    }
-#undef S2T2_LAUNCH
+    using KP = void (*)(c3s2::Args);
+#define S2T2_GATES(NCB_, G_)                                                                        \
+  {                                                                                                 \
+    c3s2::conv3x3s2_t2_kernel<NCB_, 0, G_>, c3s2::conv3x3s2_t2_kernel<NCB_, 1, G_>,                 \
+        c3s2::conv3x3s2_t2_kernel<NCB_, 2, G_>, c3s2::conv3x3s2_t2_kernel<NCB_, 3, G_>              \
+  }
+    static const KP kp[3][2][4] = {{S2T2_GATES(8, 0), S2T2_GATES(4, 0)},
+                                   {S2T2_GATES(8, 1), S2T2_GATES(4, 1)},
+                                   {S2T2_GATES(8, 2), S2T2_GATES(4, 2)}};
+#undef S2T2_GATES
+    hipLaunchKernelGGL(kp[geo][g64 ? 1 : 0][gate], dim3((unsigned)g2), dim3(256), 0, st, a2);
   } else if (g_s2_abl && cout == 64 && gate == 1) {  // timing ablations of the general kernel (abl + 100)
     switch (g_s2_abl - 100) {
       case 1: hipLaunchKernelGGL((c3s2::conv3x3s2_kernel<4, 1, 1>), dim3((unsigned)grid), dim3(c3s2::NT), 0, st, a); break;
