@@ -221,6 +221,20 @@ int yolosod_scale_boxes(float* det, const int* counts, int B, int D, const float
  * 1..65535; 16-byte accesses when A % 4 == 0 and y, merged are 16-byte aligned. */
 int yolosod_tile_merge(const float* y, int n, int nc, int A, const int32_t* desc, int rows, float* merged, int F,
                        int S, float cut_margin, void* stream);
+/* BaseValidator.match_predictions over box_iou   ultralytics/engine/validator.py:222-262 (greedy path),
+ * ultralytics/utils/metrics.py:52-71, for a whole batch of padded NMS rows in one launch, no host sync
+ * (csrc/eval_match.hip). det: [B][D][6] padded NMS rows (x1, y1, x2, y2, conf, cls), counts: device [B]. labels:
+ * device [L][5] = cls, x1, y1, x2, y2, the images' labels back to back (may be null when there are none); label_off:
+ * device [B+1], label_off[0] = 0, image b owns labels [label_off[b], label_off[b+1]) - the caller vouches that they lie
+ * inside labels. iouv: HOST array of T thresholds (they travel by value in the kernel arguments). tp: [B][D][T] bytes.
+ * Per image, in fp32 without FMA contraction and with IEEE division: iou = inter / (((a_l + a_d) - inter) + 1e-7f), 0
+ * where the classes differ; bi[d] = the best IoU of row d over the labels and best[d] the label that attains it (the
+ * highest index on a tie, none if bi[d] == 0); m[d] = the largest bi of an earlier row with the same best label, or 0;
+ * tp[d][t] = bi[d] >= iouv[t] && iouv[t] > m[d]. Every byte of tp is written exactly once; rows >= counts[b] and images
+ * without labels are 0; no atomics: deterministic. Refused: a null det / counts / label_off / iouv / tp, B < 1, D
+ * outside 1..1024, T outside 1..16, a threshold that is <= 0 or not finite. */
+int yolosod_match_predictions(const float* det, const int* counts, int B, int D, const float* labels,
+                              const int* label_off, const float* iouv, int T, uint8_t* tp, void* stream);
 
 /* Conv epilogue for the PyTorch-ROCm backbone convs (not a reference hot-path op; conv.py:37-55 + block.py:343-356
  * + Concat): out[b*out_bstride + c*HW + p] = act(y[b*y_bstride + c*HW + p] + bias[c]) (+ res[...]); act 0 id, 1 SiLU.

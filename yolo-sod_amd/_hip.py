@@ -13,6 +13,8 @@ from pathlib import Path
 
 import torch
 
+from .utils.metrics import IOU_THRESHOLDS
+
 LIB_PATH = Path(__file__).resolve().parent / "lib" / "libyolosod_hip.so"
 
 _c_float_p = ctypes.c_void_p
@@ -54,6 +56,7 @@ SIGNATURES = {
     "yolosod_letterbox_ingest": (_i, [_vp, _i, _vp, _l, _i, _i, _i, _i, _vp]),
     "yolosod_scale_boxes": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "yolosod_tile_merge": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _f, _vp]),
+    "yolosod_match_predictions": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "yolosod_stem_workspace": (_sz, [_i, _i, _i, _i]),
     "yolosod_stem_conv": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _vp, _vp, _sz, _vp]),
     "yolosod_conv1x1_thin_stats": (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _l, _i, _vp, _vp, _vp, _vp]),
@@ -1237,6 +1240,66 @@ def tile_merge(y, rows, merged, A, cut_margin=None):
     _check(_launch(("tile_merge", (n, no, A), (F, S)), dev, lib.yolosod_tile_merge, y.data_ptr(), n, nc, A,
                    d.data_ptr(), len(rows), merged.data_ptr(), F, S, cm, _stream(dev)), "tile_merge")
     return merged
+
+
+EVAL_MATCH_LABEL_CHUNK = 256  # labels staged through LDS per pass (csrc/eval_match.hip ematch::CHUNK)
+EVAL_MATCH_MAX_D = 1024       # detection rows per image (one lane each)
+EVAL_MATCH_MAX_T = 16         # IoU thresholds (by value in the kernel arguments)
+
+
+def match_predictions(out, counts, labels, label_off, iouv=IOU_THRESHOLDS):
+    """The true-positive matrix of a batch of padded NMS rows against its labels, one launch and no host sync
+    (yolosod_match_predictions, the reference's ``match_predictions`` over ``box_iou``): ``out`` [B, D, 6] fp32 and
+    ``counts`` [B] int32 as ``non_max_suppression_padded`` / ``predict_padded`` return them, ``labels`` [L, 5] fp32 =
+    (cls, x1, y1, x2, y2) of all images back to back in the boxes' own space, ``label_off`` [B + 1] int32 with image b
+    owning labels [label_off[b], label_off[b + 1]) (``engine.validator.pack_labels`` builds both), ``iouv`` the T
+    thresholds on the host (a CPU tensor, an array or a sequence; 1..16 finite values > 0). Returns tp, uint8
+    [B, D, T] on ``out``'s device: rows >= counts[b] are 0.
+
+    ``label_off`` is read on the device (reading it here would sync), so that it stays inside ``labels`` is the
+    caller's word; everything else the kernel relies on is checked here first: nothing is launched on arguments that
+    fail."""
+    import numpy as np
+    lib = load_library()
+    for t, name, dtype, dim in ((out, "out", torch.float32, 3), (counts, "counts", torch.int32, 1),
+                                (labels, "labels", torch.float32, 2), (label_off, "label_off", torch.int32, 1)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"match_predictions: {name}: expected a tensor")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"match_predictions: {name}: HIP kernel requires a GPU tensor (got device {t.device}); "
+                               "no CPU fallback")
+        if t.dtype != dtype:
+            raise RuntimeError(f"match_predictions: {name}: expected {dtype}, got {t.dtype}")
+        if t.dim() != dim:
+            raise RuntimeError(f"match_predictions: {name}: expected {dim} dimensions, got shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"match_predictions: {name}: expected a contiguous tensor")
+        if t.device != out.device:
+            raise RuntimeError(f"match_predictions: out on {out.device}, {name} on {t.device}")
+    B, D = int(out.shape[0]), int(out.shape[1])
+    if B < 1 or not 1 <= D <= EVAL_MATCH_MAX_D or int(out.shape[2]) != 6:
+        raise RuntimeError(f"match_predictions: out {tuple(out.shape)} unsupported ([B >= 1, 1..{EVAL_MATCH_MAX_D}, 6])")
+    if tuple(counts.shape) != (B,) or tuple(label_off.shape) != (B + 1,):
+        raise RuntimeError(f"match_predictions: counts {tuple(counts.shape)} / label_off {tuple(label_off.shape)} do "
+                           f"not match {B} images ([{B}] and [{B + 1}] expected)")
+    if int(labels.shape[1]) != 5:
+        raise RuntimeError(f"match_predictions: labels {tuple(labels.shape)} is not [L, 5] (cls, x1, y1, x2, y2)")
+    if isinstance(iouv, torch.Tensor):
+        if iouv.device.type != "cpu":
+            raise RuntimeError(f"match_predictions: iouv lives on the host (got device {iouv.device})")
+        iouv = iouv.detach().numpy()
+    thr = np.ascontiguousarray(np.asarray(iouv, dtype=np.float32).reshape(-1))
+    T = int(thr.size)
+    if not 1 <= T <= EVAL_MATCH_MAX_T:
+        raise RuntimeError(f"match_predictions: {T} thresholds (1..{EVAL_MATCH_MAX_T})")
+    if not (np.isfinite(thr).all() and (thr > 0).all()):
+        raise RuntimeError(f"match_predictions: thresholds {thr.tolist()} (finite and > 0 expected)")
+    dev = out.device
+    tp = torch.empty((B, D, T), dtype=torch.uint8, device=dev)
+    _check(_launch(("match_predictions", (B, D, T), int(labels.shape[0])), dev, lib.yolosod_match_predictions,
+                   out.data_ptr(), counts.data_ptr(), B, D, labels.data_ptr() if labels.shape[0] else None,
+                   label_off.data_ptr(), thr.ctypes.data, T, tp.data_ptr(), _stream(dev)), "match_predictions")
+    return tp
 
 
 def gemm_f32(A, B, b_kcontig, bias=None, bias_mode=0, act=0, res=None):
