@@ -278,14 +278,31 @@ struct GeoD : Geo<G> {
   static constexpr int PL = HH * B::RS * PS;  // plane (halves)
   static constexpr int NQUAD = NPXH * 8, NIT = (NQUAD + NT - 1) / NT;
   static_assert(NBLK <= 16 && B::RS >= HW_ && NIT <= 11 && HW_ < 256 && HH < 256, "conv3x3 geometry");
+  // wide staging (YS_C3_WIDE_STAGE): items of (quad, halo row, aligned group of four pixels). The NMG groups of a row
+  // that start inside the tile give all four pixels; the group before the tile gives its last pixel (halo column 0)
+  // and the group after it its first (halo column TW + 1). The whole groups come first, the edge groups after them,
+  // so an item's kind is fixed by its place i in the unrolled item loop except in the one place that holds both.
+  static constexpr int NMG = TW / 4, NMID = 8 * HH * NMG, NWQ = NMID + 8 * HH * 2, NITW = (NWQ + NT - 1) / NT;
+  static_assert(TW % 4 == 0 && NITW <= 4 && TW + 8 < 256, "conv3x3 wide staging");
 };
+
+// YS_C3_WIDE_STAGE (diagnostic builds: -DYS_C3_WIDE_STAGE=0 is the staging of one 4-byte load per (channel, halo
+// pixel)): the halo is loaded as aligned groups of four pixels, one 16-byte buffer load per channel of a quad. W % 4
+// == 0 and 16-byte aligned images make a group lie wholly inside or outside the image row and the buffer range; a
+// group past a row's end reads the neighbouring row (in range) or nothing (out of range), and the item's okb bit
+// replaces it by zeros. The LDS planes, the split and every MFMA operand are those of the narrow staging.
+#ifndef YS_C3_WIDE_STAGE
+#define YS_C3_WIDE_STAGE 1
+#endif
 
 template <int G, int CBW, bool RES>
 __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
   using Ge = GeoD<G>;
   constexpr int BW = Ge::BW, BH = Ge::BH, TBX = Ge::TBX, NBLK = Ge::NBLK, RS = Ge::RS;
   constexpr int TH = Ge::TH, TW = Ge::TW, HH = Ge::HH, HW_ = Ge::HW_, NPXH = Ge::NPXH, PL = Ge::PL;
-  constexpr int NQUAD = Ge::NQUAD, NIT = Ge::NIT;
+  constexpr bool WIDE = YS_C3_WIDE_STAGE != 0;
+  constexpr int NMG = Ge::NMG, NMID = Ge::NMID;
+  constexpr int NQUAD = WIDE ? Ge::NWQ : Ge::NQUAD, NIT = WIDE ? Ge::NITW : Ge::NIT;
   __shared__ __attribute__((aligned(16))) h16_t Pl[2 * PL];
   __shared__ float bsh[512];  // every output channel's bias: an epilogue load would wait behind the prefetches
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -314,10 +331,27 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
 #pragma unroll
   for (int i = 0; i < NIT; ++i) {
     const int e = min(tid + NT * i, NQUAD - 1);
-    const int quad = e / NPXH, px = e - quad * NPXH;
-    const int hy = px / HW_, hx = px - hy * HW_;
-    pk[i] = (quad << 16) | (hy << 8) | hx;
-    el0[i] = 4 * quad * HWi + hy * W + hx;
+    if constexpr (WIDE) {
+      // sixteen consecutive lanes (one lane group of a ds_write_b64) take the 8 quads of two pixel groups: the quads
+      // are 8 different bank pairs and the two groups at most a 2-way conflict (whole groups of a geometry start at
+      // pixels equal mod 4, that is on the same banks)
+      int quad, hy, gx;
+      if (e < NMID) {
+        const int f = (e >> 4) * 2 + (e & 1);  // pixel group of the tile
+        quad = (e >> 1) & 7;
+        hy = f / NMG, gx = 4 * (f % NMG);
+      } else {
+        const int e2 = e - NMID;
+        quad = e2 & 7, gx = ((e2 >> 3) & 1) ? TW : -4, hy = e2 >> 4;
+      }
+      pk[i] = (quad << 16) | (hy << 8) | (gx + 4);
+      el0[i] = 4 * quad * HWi + hy * W + gx;
+    } else {
+      const int quad = e / NPXH, px = e - quad * NPXH;
+      const int hy = px / HW_, hx = px - hy * HW_;
+      pk[i] = (quad << 16) | (hy << 8) | hx;
+      el0[i] = 4 * quad * HWi + hy * W + hx;
+    }
   }
   struct It {
     int b, ty, tx, q, grp;
@@ -333,15 +367,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
     r.b = t / (p.tiles_x * p.tiles_y);
     return r;
   };
-  f32x4 sv[NIT];
+  // narrow: sv[i][0] the item's pixel (4 channels); wide: sv[i][c] the group's four pixels of channel c
+  f32x4 sv[NIT][WIDE ? 4 : 1];
   unsigned okb_ld = 0;
   auto load_part = [&](const It& r, int k0, int k1) __attribute__((always_inline)) {
-    const int iy0 = TH * r.ty - 1, ix0 = TW * r.tx - 1;
+    const int iy0 = TH * r.ty - 1, ix0 = TW * r.tx - (WIDE ? 4 : 1);  // wide: pk's columns count from TW tx - 4
     const __amdgpu_buffer_rsrc_t ri =
         rsrc(p.x + (long)r.b * p.xbs + (long)32 * r.q * HWi, (unsigned)((p.cin - 32 * r.q) * HWi * 4));
-    const int toff = iy0 * W + ix0;
+    const int toff = iy0 * W + (WIDE ? TW * r.tx : ix0);  // wide: el0's columns count from TW tx
     if (k0 == 0) {
-      const bool interior = iy0 >= 0 && ix0 >= 0 && iy0 + HH <= H && ix0 + HW_ <= W;
+      const bool interior = iy0 >= 0 && ix0 >= 0 && iy0 + HH <= H && TW * r.tx + TW + (WIDE ? 4 : 1) <= W;
       unsigned okb = 0xffffffffu;
       if (!interior) {
         okb = 0;
@@ -356,12 +391,28 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
       if (4 * i + 3 < k0 || 4 * i >= k1) continue;
-      const unsigned vo = (unsigned)((el0[i] + toff) * 4);
+      unsigned vo = (unsigned)((el0[i] + toff) * 4);
+      // a masked group (past a ragged tile's image edge: half of the last tile column of an 80-wide map) goes out of
+      // the buffer range instead: no memory access for values that are replaced by zeros anyway
+      if constexpr (WIDE) vo = ((okb_ld >> i) & 1u) ? vo : 0xfffffff0u;
 #pragma unroll
       for (int c = 0; c < 4; ++c)
-        if (4 * i + c >= k0 && 4 * i + c < k1)
-          sv[i][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ri, vo + c * HWi * 4, 0, 0));
+        if (4 * i + c >= k0 && 4 * i + c < k1) {
+          if constexpr (WIDE)
+            sv[i][c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ri, vo + c * HWi * 4, 0, 0));
+          else
+            sv[i][0][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(ri, vo + c * HWi * 4, 0, 0));
+        }
     }
+  };
+  // one staged pixel (4 channels of a quad): split, range, the two planes
+  auto put = [&](int px, int quad, f32x4 v) __attribute__((always_inline)) {
+    uint2 hh, ll;
+    split4x(v, hh, ll);
+    rng = range_acc(rng, v);
+    h16_t* d = Pl + px * PS + 4 * quad;
+    *reinterpret_cast<uint2*>(d) = hh;
+    *reinterpret_cast<uint2*>(d + PL) = ll;
   };
   const int rp = wid & 1, ph = wid >> 1;
   int bpx[8];
@@ -380,7 +431,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
   for (int r = 0; r < CBW; ++r)
 #pragma unroll
     for (int cb = 0; cb < 8; ++cb) acc[r][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
-  constexpr int NLD = 4 * NIT;             // loads per (tile, chunk): 44
+  constexpr int NLD = 4 * NIT;             // loads per (tile, chunk): 16 / 16 / 12 of 16 bytes (narrow: 44 / 40 / 44 of 4)
   constexpr int PER_TAP = (NLD + 8) / 9;   // spread over the nine taps
 
   It cur = it_of(0);
@@ -394,14 +445,27 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
       const int e = tid + NT * i;
       if (e < NQUAD) {
         const int quad = pk[i] >> 16;
-        const int px = RS == HW_ ? e - quad * NPXH : ((pk[i] >> 8) & 255) * RS + (pk[i] & 255);
-        const f32x4 v = ((okb >> i) & 1u) ? sv[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-        uint2 hh, ll;
-        split4x(v, hh, ll);
-        rng = range_acc(rng, v);
-        h16_t* d = Pl + px * PS + 4 * quad;
-        *reinterpret_cast<uint2*>(d) = hh;
-        *reinterpret_cast<uint2*>(d + PL) = ll;
+        const bool ok = (okb >> i) & 1u;
+        const f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
+        if constexpr (WIDE) {
+          // place i of the item loop holds whole groups, edge groups or (one place) both
+          const bool all_mid = NT * i + NT <= NMID, all_edge = NT * i >= NMID;  // constants once unrolled
+          const bool mid = all_mid || (!all_edge && e < NMID);
+          const int g4 = pk[i] & 255;  // 0: the group before the tile (its last pixel is halo column 0)
+          const int px = ((pk[i] >> 8) & 255) * RS + max(g4 - 3, 0);
+          f32x4 v = f32x4{sv[i][0][0], sv[i][1][0], sv[i][2][0], sv[i][3][0]};
+          if (!all_mid && g4 == 0)
+            v = f32x4{sv[i][0][3], sv[i][1][3], sv[i][2][3], sv[i][3][3]};
+          put(px, quad, ok ? v : z);
+          if (mid) {
+#pragma unroll
+            for (int jx = 1; jx < 4; ++jx)
+              put(px + jx, quad, ok ? f32x4{sv[i][0][jx], sv[i][1][jx], sv[i][2][jx], sv[i][3][jx]} : z);
+          }
+        } else {
+          const int px = RS == HW_ ? e - quad * NPXH : ((pk[i] >> 8) & 255) * RS + (pk[i] & 255);
+          put(px, quad, ok ? sv[i][0] : z);
+        }
       }
     }
     __syncthreads();
@@ -650,8 +714,10 @@ YS_EXPORT int yolosod_conv3x3_silu_xs(const float* x, long x_bstride, float* y, 
   const long nwg = (long)B * a.tiles_x * a.tiles_y * ngrp;
   YS_CHECK_ARG(nwg < (1L << 31), "conv3x3: too many tiles");
   hipStream_t st = (hipStream_t)stream;
-  // the persistent kernel for W % 4 == 0 (two workgroups per CU); the one-tile-per-workgroup kernel otherwise
-  if (v4 && g_c3_abl == 0) {
+  // the persistent kernel for W % 4 == 0 (two workgroups per CU); the one-tile-per-workgroup kernel otherwise (and
+  // for input images that are not 16-byte aligned, which the wide staging's loads need: no tensor of the model)
+  const bool x16 = YS_C3_WIDE_STAGE == 0 || (((uintptr_t)x & 15) == 0 && x_bstride % 4 == 0);
+  if (v4 && x16 && g_c3_abl == 0) {
     const int fgrp = (g_c3_form >> 2) & 3;
     YS_CHECK_ARG(!(fgrp == 1 && cout == 32), "conv3x3: 32 outputs have no 64-channel group form");
     const int form = c3_form(B, cout, H, W);
