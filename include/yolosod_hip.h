@@ -405,12 +405,17 @@ int yolosod_debug_set_conv3x3_abl(int abl);
  * every form gives bit-identical results. form = geometry + 4 * groups. geometry: 0 automatic (the fewest tiles for
  * the map), 1 the 32 x 8 tile of 16 x 1 blocks, 2 the 20 x 12 tile of 4 x 4 blocks, 3 the 40 x 6 tile of 8 x 2
  * blocks. groups: 0 automatic (32-channel groups when 64-channel work items would leave workgroup slots idle), 1
- * 64-channel output groups (an error for Cout 32), 2 32-channel groups. Values outside [0, 12) are ignored. Returns
- * the previous value. */
+ * 64-channel output groups (an error for Cout 32), 2 32-channel groups, 3 the 32-channel group with the wave's whole
+ * weight set resident in registers (Cin 32 -> Cout 32; any other shape runs groups 2), 4 the 32-channel group with
+ * both 16-channel blocks on every wave (Cout 32; any other Cout runs groups 2). Values outside [0, 20) are ignored.
+ * Returns the previous value. */
 int yolosod_debug_set_conv3x3_form(int form);
 /* The form (same encoding, no field 0) a [B][*][H][W] -> cout launch of yolosod_conv3x3_silu* runs in under the current
  * setting; 0 for shapes the persistent kernel does not take (W % 4 != 0, unsupported cout). */
 int yolosod_debug_conv3x3_form(int B, int cout, int H, int W);
+/* As yolosod_debug_conv3x3_form for a known Cin: groups 3 / 4 are chosen (automatically, or forced) for Cin 32 ->
+ * Cout 32 only, and yolosod_debug_conv3x3_form answers for every other Cin. */
+int yolosod_debug_conv3x3_form_ex(int B, int cin, int cout, int H, int W);
 void yolosod_debug_set_gemm_x2(int on);
 /* Test hook: the bf16 decomposed SwinBlock's depthwise conv + token layout and LN1 in one pass
  * (swin_tokens_ln_bf16_kernel, 1, default) or as two kernels (0);

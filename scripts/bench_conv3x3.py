@@ -63,7 +63,10 @@ lib = _hip.load_library()
 FORMS = [0]
 if len(sys.argv) > 1 and sys.argv[1] == "forms" and hasattr(lib, "yolosod_debug_set_conv3x3_form"):
     FORMS = [0] + [g + 4 * grp for g in (1, 2, 3) for grp in (1, 2)]
+    if hasattr(lib, "yolosod_debug_conv3x3_form_ex"):  # Cin 32 -> Cout 32: resident weights (3), both blocks per wave (4)
+        FORMS += [g + 4 * grp for g in (1, 2, 3) for grp in (3, 4)]
 GEO = {1: "32x8", 2: "20x12", 3: "40x6"}
+GRP = {1: "g64", 2: "g32", 3: "g32r", 4: "g32b"}
 
 for shape, cout, res in CASES:
     B, cin, H, W = shape
@@ -76,15 +79,18 @@ for shape, cout, res in CASES:
     t_m = timed(lambda: _hip.bias_act(F.conv2d(x, w, None, padding=1), b, 1, res=r))
     line = f"{str(shape):22s} -> {cout:3d}{' +res' if res else '     '}  MIOpen+epilogue {t_m:7.3f} ms ({gf / t_m:6.1f} TF/s)"
     for form in FORMS:
-        if form and cout == 32 and form >> 2 == 1:
+        if form and (cout == 32 and form >> 2 == 1 or form >> 2 > 2 and (cout, cin) != (32, 32)):
             continue
         if len(FORMS) > 1:
             lib.yolosod_debug_set_conv3x3_form(form)
         t_k = timed(lambda: _hip.conv3x3_silu(x, b, lambda: prep, cout, res=r))
         name = "kernel"
-        if hasattr(lib, "yolosod_debug_conv3x3_form"):
+        if hasattr(lib, "yolosod_debug_conv3x3_form_ex"):
+            f = lib.yolosod_debug_conv3x3_form_ex(B, cin, cout, H, W)
+            name = f"{'auto=' if form == 0 else ''}{GEO[f & 3]}/{GRP[f >> 2]}"
+        elif hasattr(lib, "yolosod_debug_conv3x3_form"):
             f = lib.yolosod_debug_conv3x3_form(B, cout, H, W)
-            name = f"{'auto=' if form == 0 else ''}{GEO[f & 3]}/g{32 * (3 - (f >> 2))}"
+            name = f"{'auto=' if form == 0 else ''}{GEO[f & 3]}/{GRP[f >> 2]}"
         line += f"   {name} {t_k:6.3f} ms ({gf / t_k:5.1f} TF/s)"
     if len(FORMS) > 1:
         lib.yolosod_debug_set_conv3x3_form(0)

@@ -107,6 +107,7 @@ SIGNATURES = {
     "yolosod_debug_set_conv3x3_abl": (_i, [_i]),
     "yolosod_debug_set_conv3x3_form": (_i, [_i]),
     "yolosod_debug_conv3x3_form": (_i, [_i, _i, _i, _i]),
+    "yolosod_debug_conv3x3_form_ex": (_i, [_i, _i, _i, _i, _i]),
     "yolosod_debug_set_conv3x3s2_abl": (_i, [_i]),
     "yolosod_debug_set_conv3x3s2_form": (_i, [_i]),
     "yolosod_debug_conv3x3s2_form": (_i, [_i, _i, _i, _i]),

@@ -295,8 +295,18 @@ struct GeoD : Geo<G> {
 #define YS_C3_WIDE_STAGE 1
 #endif
 
-template <int G, int CBW, bool RES>
-__global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
+// F: the wave layout / weight path of a 32-channel output group (CBW == 1; every F is bit-identical, see above).
+//   F 0: wave w = (row-half w >> 1: 8 block slots) x (channel block w & 1); weight fragments from L2, one tap ahead.
+//   F 1: F 0's layout with the wave's whole weight set (9 taps x 2 planes: 72 VGPRs) loaded once before the item
+//        loop. Cin 32 and Cout 32 only (one chunk, one group: the set never changes); the tap loop issues no weight
+//        load, so the only vector-memory loads in flight in it are the next iteration's halo.
+//   F 2: wave w = block slots 4 w .. 4 w + 3 x both channel blocks: a pixel fragment read from LDS feeds six MFMAs
+//        instead of three (8 ds_read_b128 per wave and tap instead of 16); weight fragments from L2, one tap ahead.
+template <int G, int CBW, bool RES, int F>
+__device__ __forceinline__ void conv3x3_p_body(const Args& p) {
+  static_assert(F == 0 || CBW == 1, "conv3x3: F 1 / F 2 are forms of the 32-channel group");
+  constexpr int NS = F == 2 ? 4 : 8;    // block slots per wave
+  constexpr int CW = F == 2 ? 2 : CBW;  // 16-channel blocks per wave
   using Ge = GeoD<G>;
   constexpr int BW = Ge::BW, BH = Ge::BH, TBX = Ge::TBX, NBLK = Ge::NBLK, RS = Ge::RS;
   constexpr int TH = Ge::TH, TW = Ge::TW, HH = Ge::HH, HW_ = Ge::HW_, NPXH = Ge::NPXH, PL = Ge::PL;
@@ -307,7 +317,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
   __shared__ float bsh[512];  // every output channel's bias: an epilogue load would wait behind the prefetches
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, g = lane >> 4;
-  const int H = p.H, W = p.W, HWi = H * W, nq = p.cin >> 5;
+  const int H = p.H, W = p.W, HWi = H * W, nq = F == 1 ? 1 : p.cin >> 5;
   float rng = 0.f;
   for (int o = tid; o < 16 * p.ncb_all; o += 256) bsh[o] = p.bias[o];  // ordered before use by the loop's barriers
 
@@ -414,11 +424,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
     *reinterpret_cast<uint2*>(d) = hh;
     *reinterpret_cast<uint2*>(d + PL) = ll;
   };
-  const int rp = wid & 1, ph = wid >> 1;
-  int bpx[8];
+  const int rp = F == 2 ? 0 : wid & 1, slot0 = F == 2 ? 4 * wid : 8 * (wid >> 1);
+  int bpx[NS];
 #pragma unroll
-  for (int cb = 0; cb < 8; ++cb) {
-    const int bi = 8 * ph + cb < NBLK ? 8 * ph + cb : 0;  // a slot past the tile's blocks recomputes block 0, unstored
+  for (int cb = 0; cb < NS; ++cb) {
+    const int bi = slot0 + cb < NBLK ? slot0 + cb : 0;  // a slot past the tile's blocks recomputes block 0, unstored
     bpx[cb] = ((bi / TBX) * BH + l15 / BW) * RS + (bi % TBX) * BW + l15 % BW;
   }
   auto wfrag = [&](int t, int q, int cbw, int pl) __attribute__((always_inline)) {
@@ -426,11 +436,19 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
     return __builtin_bit_cast(f16x8_t, __builtin_amdgcn_raw_buffer_load_b128(
                                            rw, (unsigned)(((cbw * 2 + pl) * 64 + lane) * 16), st, 0));
   };
-  f32x4 acc[CBW][8];
+  f32x4 acc[CW][NS];
 #pragma unroll
-  for (int r = 0; r < CBW; ++r)
+  for (int r = 0; r < CW; ++r)
 #pragma unroll
-    for (int cb = 0; cb < 8; ++cb) acc[r][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int cb = 0; cb < NS; ++cb) acc[r][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+  f16x8_t wres[F == 1 ? 9 : 1][2];  // F 1: the wave's weight set (channel block rp of the one group), resident
+  if constexpr (F == 1) {
+#pragma unroll
+    for (int t = 0; t < 9; ++t) {
+      wres[t][0] = wfrag(t, 0, rp, 0);
+      wres[t][1] = wfrag(t, 0, rp, 1);
+    }
+  }
   constexpr int NLD = 4 * NIT;             // loads per (tile, chunk): 16 / 16 / 12 of 16 bytes (narrow: 44 / 40 / 44 of 4)
   constexpr int PER_TAP = (NLD + 8) / 9;   // spread over the nine taps
 
@@ -451,6 +469,14 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
           // place i of the item loop holds whole groups, edge groups or (one place) both
           const bool all_mid = NT * i + NT <= NMID, all_edge = NT * i >= NMID;  // constants once unrolled
           const bool mid = all_mid || (!all_edge && e < NMID);
+          // A place of edge groups only uses one pixel of each 16-byte load. The register allocator then gives the two
+          // unused registers of a load's destination to values written while the load is in flight (the next load's
+          // address), and the write-after-write wait it needs is a vmcnt(0) inside the tap loop: every halo load in
+          // flight, the one just issued included. An empty statement (no instruction) keeps all four registers live.
+          if (all_edge) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) asm volatile("" : "+v"(sv[i][c]));
+          }
           const int g4 = pk[i] & 255;  // 0: the group before the tile (its last pixel is halo column 0)
           const int px = ((pk[i] >> 8) & 255) * RS + max(g4 - 3, 0);
           f32x4 v = f32x4{sv[i][0][0], sv[i][1][0], sv[i][2][0], sv[i][3][0]};
@@ -472,11 +498,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
     // the last iteration reloads itself (unconditional loads; L2-hot)
     if (it + 1 < n_it) cur = it_of(it + 1);
     const int cbw0 = r.grp * 2 * CBW + CBW * rp;
-    f16x8_t wa[CBW][2], wn[CBW][2];
+    f16x8_t wa[CW][2], wn[CW][2];
+    if constexpr (F != 1) {
 #pragma unroll
-    for (int u = 0; u < CBW; ++u) {
-      wa[u][0] = wfrag(0, r.q, cbw0 + u, 0);
-      wa[u][1] = wfrag(0, r.q, cbw0 + u, 1);
+      for (int u = 0; u < CW; ++u) {
+        wa[u][0] = wfrag(0, r.q, cbw0 + u, 0);
+        wa[u][1] = wfrag(0, r.q, cbw0 + u, 1);
+      }
     }
     // pixel fragments one (tap, pixel block) step ahead of their MFMAs (across taps too), and group barriers that
     // keep each step's two LDS reads ahead of the previous step's MFMAs: without them the reads sit right before
@@ -492,48 +520,54 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
 #pragma unroll
     for (int t = 0; t < 9; ++t) {
       const int tn = t + 1 < 9 ? t + 1 : t;
+      if constexpr (F != 1) {
 #pragma unroll
-      for (int u = 0; u < CBW; ++u) {
-        wn[u][0] = wfrag(tn, r.q, cbw0 + u, 0);
-        wn[u][1] = wfrag(tn, r.q, cbw0 + u, 1);
+        for (int u = 0; u < CW; ++u) {
+          wn[u][0] = wfrag(tn, r.q, cbw0 + u, 0);
+          wn[u][1] = wfrag(tn, r.q, cbw0 + u, 1);
+        }
       }
       load_part(cur, PER_TAP * t, min(PER_TAP * t + PER_TAP, NLD));
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int cb = 0; cb < 8; ++cb) {
+      for (int cb = 0; cb < NS; ++cb) {
         const f16x8_t xh = nh, xlo = nl;
-        if (cb < 7) rd(t, cb + 1, nh, nl);
+        if (cb < NS - 1) rd(t, cb + 1, nh, nl);
         else if (t < 8) rd(t + 1, 0, nh, nl);
 #pragma unroll
-        for (int u = 0; u < CBW; ++u) {
-          f32x4 c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wa[u][1], acc[u][cb], 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xlo, wa[u][0], c, 0, 0, 0);
-          acc[u][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wa[u][0], c, 0, 0, 0);
+        for (int u = 0; u < CW; ++u) {
+          const f16x8_t w0 = F == 1 ? wres[F == 1 ? t : 0][0] : wa[u][0];
+          const f16x8_t w1 = F == 1 ? wres[F == 1 ? t : 0][1] : wa[u][1];
+          f32x4 c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, w1, acc[u][cb], 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xlo, w0, c, 0, 0, 0);
+          acc[u][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, w0, c, 0, 0, 0);
         }
       }
 #pragma unroll
-      for (int cb = 0; cb < 8; ++cb) {
-        if (cb < 7 || t < 8) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read
-        __builtin_amdgcn_sched_group_barrier(0x008, 3 * CBW, 0);                 // MFMA
+      for (int cb = 0; cb < NS; ++cb) {
+        if (cb < NS - 1 || t < 8) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read
+        __builtin_amdgcn_sched_group_barrier(0x008, 3 * CW, 0);                       // MFMA
       }
+      if constexpr (F != 1) {
 #pragma unroll
-      for (int u = 0; u < CBW; ++u) {
-        wa[u][0] = wn[u][0];
-        wa[u][1] = wn[u][1];
+        for (int u = 0; u < CW; ++u) {
+          wa[u][0] = wn[u][0];
+          wa[u][1] = wn[u][1];
+        }
       }
     }
     if (r.q == nq - 1) {
       float* yb = p.y + (long)r.b * p.ybs;
-      float bv[CBW];
+      float bv[CW];
 #pragma unroll
-      for (int u = 0; u < CBW; ++u) bv[u] = bsh[16 * (cbw0 + u) + l15];
+      for (int u = 0; u < CW; ++u) bv[u] = bsh[16 * (cbw0 + u) + l15];
 #pragma unroll
-      for (int cb = 0; cb < 8; ++cb) {
-        const int bi = 8 * ph + cb;
+      for (int cb = 0; cb < NS; ++cb) {
+        const int bi = slot0 + cb;
         const int oy = r.ty * TH + (bi / TBX) * BH + (4 * g) / BW, ox = r.tx * TW + (bi % TBX) * BW + (4 * g) % BW;
         const bool live = (NBLK == 16 || bi < NBLK) && oy < H && ox < W;
 #pragma unroll
-        for (int u = 0; u < CBW; ++u) {
+        for (int u = 0; u < CW; ++u) {
           const long po = (long)(16 * (cbw0 + u) + l15) * HWi + oy * W + ox;
           f32x4 o;
 #pragma unroll
@@ -550,6 +584,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
   }
   range_report(p.range_flag, rng);
   if (p.prep_flag && p.range_flag && blockIdx.x == 0 && threadIdx.x == 0 && *p.prep_flag) *p.range_flag = 1u;
+}
+
+template <int G, int CBW, bool RES>
+__global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
+  conv3x3_p_body<G, CBW, RES, 0>(p);
+}
+
+// The F 1 / F 2 forms of the 32-channel group (Cout 32: layer 3's and the neck's P2 Bottleneck convs).
+template <int G, bool RES, int F>
+__global__ __launch_bounds__(256, 2) void conv3x3_c32_kernel(Args p) {
+  conv3x3_p_body<G, 1, RES, F>(p);
 }
 
 // W [64][Cin][3][3] -> fragment-major planes of 64 W (see the file comment); one thread per (output channel, input
@@ -588,12 +633,14 @@ YS_EXPORT int yolosod_debug_set_conv3x3_abl(int abl) {
 
 // Forced form of the persistent kernel (tests / per-shape measurements compare forms; the automatic choice is the
 // product): form = geometry + 4 groups; geometry 0 automatic, 1 the 32 x 8 tile, 2 the 20 x 12 tile of 4 x 4 blocks,
-// 3 the 40 x 6 tile of 8 x 2 blocks; groups 0 automatic, 1 64-channel output groups, 2 32-channel groups. Every
-// geometry takes every W % 4 == 0 shape; 64-channel groups need Cout >= 64. Returns the previous value.
+// 3 the 40 x 6 tile of 8 x 2 blocks; groups 0 automatic, 1 64-channel output groups, 2 32-channel groups, 3 the
+// 32-channel group with the weights resident in registers (F 1: Cin 32 -> Cout 32 only), 4 the 32-channel group with
+// both channel blocks on every wave (F 2: Cout 32 only). Every geometry takes every W % 4 == 0 shape; 64-channel
+// groups need Cout >= 64. Returns the previous value.
 static int g_c3_form = 0;
 YS_EXPORT int yolosod_debug_set_conv3x3_form(int form) {
   const int old = g_c3_form;
-  if (form >= 0 && form < 12) g_c3_form = form;
+  if (form >= 0 && form < 20) g_c3_form = form;
   return old;
 }
 
@@ -628,11 +675,20 @@ static int c3_cu_count() {
 // The resolved form (geometry 1 .. 3 + 4 * groups 1 .. 2) of a W % 4 == 0 launch: the forced fields of g_c3_form, the
 // automatic choice for the others. 32-channel groups (twice the work items, each with half the MFMAs and its own
 // staging) when the 64-channel items would leave workgroup slots (two per CU) idle.
-static int c3_form(int B, int cout, int H, int W) {
-  const int fgeo = g_c3_form & 3, fgrp = (g_c3_form >> 2) & 3;
+// Cin 32 -> Cout 32 (cin 0: not known, as any other Cin) picks among the three forms of the 32-channel group by
+// C3_AUTO_C32 (groups field per geometry). Neither new form beat today's on 32 x 32 x 160^2 by more than the
+// measurement's spread (resident weights: 0.055 - 0.057 ms against 0.060 - 0.065 plain, 0.069 against 0.068 - 0.073
+// with the shortcut; both blocks per wave: 0.065 / 0.073), so none is routed: they are forms to force.
+static const int C3_AUTO_C32[3] = {2, 2, 2};
+static int c3_form(int B, int cin, int cout, int H, int W) {
+  const int fgeo = g_c3_form & 3, fgrp = g_c3_form >> 2;
   const int geo = fgeo ? fgeo - 1 : c3_pick_geo(H, W);
   const long ntiles = (long)B * ((W + C3_GEO_TW[geo] - 1) / C3_GEO_TW[geo]) * ((H + C3_GEO_TH[geo] - 1) / C3_GEO_TH[geo]);
-  const bool g32 = cout == 32 || (fgrp ? fgrp == 2 : ntiles * (cout / 64) < 2L * c3_cu_count());
+  if (cout == 32) {  // a forced form that does not apply to the shape (resident weights with Cin != 32) resolves to 2
+    const int grp = fgrp == 3 ? (cin == 32 ? 3 : 2) : fgrp == 4 ? 4 : fgrp == 0 && cin == 32 ? C3_AUTO_C32[geo] : 2;
+    return geo + 1 + 4 * grp;
+  }
+  const bool g32 = fgrp ? fgrp >= 2 : ntiles * (cout / 64) < 2L * c3_cu_count();
   return geo + 1 + 4 * (g32 ? 2 : 1);
 }
 
@@ -650,9 +706,14 @@ YS_EXPORT size_t yolosod_conv3x3_prep_bytes(int cin) { return yolosod_conv3x3_pr
 
 // The form (as yolosod_debug_set_conv3x3_form encodes it, no field 0) the persistent kernel runs a [B][*][H][W] ->
 // cout launch in under the current setting; 0 for shapes it does not take (W % 4 != 0, unsupported cout).
-YS_EXPORT int yolosod_debug_conv3x3_form(int B, int cout, int H, int W) {
+// The Cin 32 -> Cout 32 forms (groups 3 / 4) are reported by the _ex query, which knows Cin; this one answers for any
+// other Cin.
+YS_EXPORT int yolosod_debug_conv3x3_form_ex(int B, int cin, int cout, int H, int W) {
   if (B <= 0 || H <= 0 || W <= 0 || W % 4 || !c3_cout_ok(cout)) return 0;
-  return c3_form(B, cout, H, W);
+  return c3_form(B, cin, cout, H, W);
+}
+YS_EXPORT int yolosod_debug_conv3x3_form(int B, int cout, int H, int W) {
+  return yolosod_debug_conv3x3_form_ex(B, 0, cout, H, W);
 }
 
 static bool conv3x3_carve(void* buf, size_t bytes, int cin, int cout, h16_t** wp, unsigned** flag) {
@@ -718,11 +779,12 @@ YS_EXPORT int yolosod_conv3x3_silu_xs(const float* x, long x_bstride, float* y, 
   // for input images that are not 16-byte aligned, which the wide staging's loads need: no tensor of the model)
   const bool x16 = YS_C3_WIDE_STAGE == 0 || (((uintptr_t)x & 15) == 0 && x_bstride % 4 == 0);
   if (v4 && x16 && g_c3_abl == 0) {
-    const int fgrp = (g_c3_form >> 2) & 3;
+    const int fgrp = g_c3_form >> 2;
     YS_CHECK_ARG(!(fgrp == 1 && cout == 32), "conv3x3: 32 outputs have no 64-channel group form");
-    const int form = c3_form(B, cout, H, W);
+    const int form = c3_form(B, cin, cout, H, W);
     const int geo = (form & 3) - 1;
-    const bool g32 = (form >> 2) == 2;
+    const bool g32 = (form >> 2) >= 2;
+    const int fc = (form >> 2) - 2;   // the 32-channel group's F (1 / 2: Cout 32 only, c3_form)
     a.tiles_x = (W + C3_GEO_TW[geo] - 1) / C3_GEO_TW[geo];
     a.tiles_y = (H + C3_GEO_TH[geo] - 1) / C3_GEO_TH[geo];
     a.ntiles = (int)((long)B * a.tiles_x * a.tiles_y);
@@ -739,7 +801,15 @@ YS_EXPORT int yolosod_conv3x3_silu_xs(const float* x, long x_bstride, float* y, 
          {c3::conv3x3_p_kernel<1, 1, false>, c3::conv3x3_p_kernel<1, 1, true>}},
         {{c3::conv3x3_p_kernel<2, 2, false>, c3::conv3x3_p_kernel<2, 2, true>},
          {c3::conv3x3_p_kernel<2, 1, false>, c3::conv3x3_p_kernel<2, 1, true>}}};
-    hipLaunchKernelGGL(kp[geo][g32 ? 1 : 0][res ? 1 : 0], dim3((unsigned)grid), dim3(256), 0, st, a);
+    static const KP kc[3][2][2] = {
+        {{c3::conv3x3_c32_kernel<0, false, 1>, c3::conv3x3_c32_kernel<0, true, 1>},
+         {c3::conv3x3_c32_kernel<0, false, 2>, c3::conv3x3_c32_kernel<0, true, 2>}},
+        {{c3::conv3x3_c32_kernel<1, false, 1>, c3::conv3x3_c32_kernel<1, true, 1>},
+         {c3::conv3x3_c32_kernel<1, false, 2>, c3::conv3x3_c32_kernel<1, true, 2>}},
+        {{c3::conv3x3_c32_kernel<2, false, 1>, c3::conv3x3_c32_kernel<2, true, 1>},
+         {c3::conv3x3_c32_kernel<2, false, 2>, c3::conv3x3_c32_kernel<2, true, 2>}}};
+    const KP k = fc > 0 ? kc[geo][fc - 1][res ? 1 : 0] : kp[geo][g32 ? 1 : 0][res ? 1 : 0];
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(256), 0, st, a);
     YS_CHECK_LAUNCH("conv3x3");
     return 0;
   }

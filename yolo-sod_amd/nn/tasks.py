@@ -473,6 +473,7 @@ class DetectionModel(BaseModel):
                     m.s2 = True
                 elif i and m.f == -1 and not isinstance(self.model[i - 1], (M.SE, M.CBAM_Block)):
                     m.s2_backbone = True  # gate-free (not the stem, not an SE / CBAM consumer): modules.S2_BACKBONE
+                    m.layer = i           # (the switch may name layers)
             if isinstance(m, M.C2f):  # the C2fs' Bottleneck 3x3 convs (neck: S1_NECK, backbone: S1_BACKBONE)
                 for bt in m.m:
                     for cv in (bt.cv1, bt.cv2):
