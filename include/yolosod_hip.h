@@ -386,6 +386,16 @@ int yolosod_conv1x1x2_silu(const float* x, long x_bstride, float* y, long y_bstr
 int yolosod_conv1x1x2_silu_cat(const float* x, long x_bstride, const float* x2, long x2_bstride, int k1, float* y,
                                long y_bstride, float* y2, long y2_bstride, int c2lo, int B, int cin, int cout, int HW,
                                const float* bias, const void* prep, size_t prep_bytes, int up_w, void* stream);
+/* Test / measurement hook: force the form of the fp16-split 1x1 conv kernel (csrc/conv1x1x2.hip); every form gives
+ * bit-identical results. form = groups + 4 * buffers. groups: 0 automatic, 1 workgroups of 128 output channels (two
+ * 16-channel blocks per wave), 2 of 256 (four blocks per wave; Cout % 256 == 0, any other Cout runs groups 1).
+ * buffers: 0 automatic, 1 one pair of staged fp16 planes (two barriers per stage), 2 two pairs (double-buffered: one
+ * barrier per stage, 69632 B of LDS). Cout 64 has one form, reported as 1 + 4 * 1. Values outside [0, 12) and groups
+ * 3 are ignored. Returns the previous value. */
+int yolosod_debug_set_conv1x1x2_form(int form);
+/* The form (same encoding, no field 0) a [B][*][H][W] -> cout launch of yolosod_conv1x1x2_silu* runs in under the
+ * current setting; 0 for shapes the kernel does not take (H * W not a multiple of 4, unsupported cout). */
+int yolosod_debug_conv1x1x2_form(int B, int cout, int H, int W);
 /* Timing hook: ablation variants of the stride-2 conv kernel at Cout 64 with a channel gate (csrc/conv3x3s2.hip; WRONG
  * results for abl != 0 - scripts/bench_conv3x3s2.py only). Returns the previous value. */
 int yolosod_debug_set_conv3x3s2_abl(int abl);

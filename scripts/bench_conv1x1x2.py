@@ -62,5 +62,50 @@ def main():
     print(f"total n1 shapes: miopen+epi {tot_a:.3f} ms  x2 {tot_b:.3f} ms")
 
 
+def forms():
+    """python scripts/bench_conv1x1x2.py forms: every form of the kernel (yolosod_debug_set_conv1x1x2_form: groups +
+    4 buffers) forced on the neck's n1 shapes and the backbone's eight wide 1x1 shapes of the n640 step at bs 32; a
+    library given by YOLOSOD_LIB_AB that predates the hook has its one form. One line per (shape, Cout, form): run it
+    twice per library, alternating the libraries, and compare across the runs."""
+    dev = torch.device("cuda")
+    lib = _hip.load_library()
+    model = build_model("yolov12-sod-fusion-v5-simple.yaml", seed=0, device=dev)
+    # the launches of one step with every marked conv routed (C2f calls its cv1 without a module hook: the op_timer
+    # keys (op, input shape, (Cout, dual store, ...)) see every launch)
+    M.N1_BACKBONE = True
+    with torch.inference_mode(), _hip.op_timer() as rec:
+        model(torch.rand(32, 3, 640, 640, device=dev))
+    shapes = {}
+    for k, _ in rec.durations_ms():
+        if k[0] in ("conv1x1x2", "conv1x1x2_backbone") and k[2][0] % 128 == 0:
+            who = "backbone" if k[0].endswith("_backbone") else "neck"
+            where = shapes.setdefault((tuple(k[1]), k[2][0]), who)
+            if who not in where:
+                shapes[(tuple(k[1]), k[2][0])] = "both"
+    del model
+    has = hasattr(lib, "yolosod_debug_set_conv1x1x2_form")
+    g = torch.Generator().manual_seed(0)
+    with torch.inference_mode():
+        for (shape, cout), where in sorted(shapes.items(), key=lambda kv: (-kv[0][0][2], kv[0][1], kv[0][0][1])):
+            B, cin, H, W = shape
+            x = torch.randn(shape, device=dev)
+            w = (torch.randn(cout, cin, generator=g) * (1.0 / cin ** 0.5)).to(dev)
+            b = (torch.randn(cout, generator=g) * 0.1).to(dev)
+            blk = _hip.conv1x1x2_prepare(w)
+            out = torch.empty((B, cout, H, W), device=dev)
+            for form in ((5, 6, 9, 10) if has else (0,)):
+                if has:
+                    lib.yolosod_debug_set_conv1x1x2_form(form)
+                    if lib.yolosod_debug_conv1x1x2_form(B, cout, H, W) != form:
+                        continue  # the shape does not take the form
+                t = timeit(lambda: _hip.conv1x1x2_silu(x, b, lambda: blk, cout, out=out), iters=50)
+                print(f"{where:8s} {cin:5d} -> {cout:4d} at {H:3d}^2  form {form:2d}  {t:7.4f} ms", flush=True)
+            if has:
+                lib.yolosod_debug_set_conv1x1x2_form(0)
+
+
 if __name__ == "__main__":
-    main()
+    if len(sys.argv) > 1 and sys.argv[1] == "forms":
+        forms()
+    else:
+        main()

@@ -108,6 +108,8 @@ SIGNATURES = {
     "yolosod_debug_set_conv3x3_form": (_i, [_i]),
     "yolosod_debug_conv3x3_form": (_i, [_i, _i, _i, _i]),
     "yolosod_debug_conv3x3_form_ex": (_i, [_i, _i, _i, _i, _i]),
+    "yolosod_debug_set_conv1x1x2_form": (_i, [_i]),
+    "yolosod_debug_conv1x1x2_form": (_i, [_i, _i, _i, _i]),
     "yolosod_debug_set_conv3x3s2_abl": (_i, [_i]),
     "yolosod_debug_set_conv3x3s2_form": (_i, [_i]),
     "yolosod_debug_conv3x3s2_form": (_i, [_i, _i, _i, _i]),
@@ -985,9 +987,10 @@ def conv1x1x2_prepare(w):
     return blk
 
 
-def conv1x1x2_silu(x, bias, prep, cout, out=None, out2=None, c2lo=0):
+def conv1x1x2_silu(x, bias, prep, cout, out=None, out2=None, c2lo=0, op="conv1x1x2"):
     """SiLU(W x + bias) for a 1x1 conv on the fp16 two-term split MFMA (csrc/conv1x1x2.hip). ``x``, ``out`` may be
-    channel slices of concat buffers (contiguous images); ``out2``: channels [c2lo, Cout) stored again (packed)."""
+    channel slices of concat buffers (contiguous images); ``out2``: channels [c2lo, Cout) stored again (packed);
+    ``op``: the op_timer key's name (the backbone's launches are recorded as "conv1x1x2_backbone")."""
     lib = load_library()
     B, Cin, H, W = x.shape
     if out is None:
@@ -1011,7 +1014,7 @@ def conv1x1x2_silu(x, bias, prep, cout, out=None, out2=None, c2lo=0):
                                               W if x1 is not None and x.up0 else 0, _stream(x.device))
 
     extra = (cout, out2 is not None) + (("cat",) if x1 is not None else ())
-    _check(_launch(("conv1x1x2", tuple(x.shape), extra), x.device, run), "conv1x1x2")
+    _check(_launch((op, tuple(x.shape), extra), x.device, run), "conv1x1x2")
     return y
 
 

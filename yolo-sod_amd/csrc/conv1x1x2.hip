@@ -13,6 +13,12 @@
 // computes output channel blocks 2 w, 2 w + 1 for the 4 pixel blocks, pixels as the MFMA A operand (a lane holds 4
 // consecutive pixels of one channel: 16-byte stores). The next stage's loads are spread over the current stage's
 // k steps behind each step's weight prefetch (vmcnt counts in issue order); sched barriers keep them there.
+//
+// Forms (yolosod_debug_set_conv1x1x2_form; every form adds an output element's products in the same order, so all are
+// bit-identical): a wave may own four 16-channel blocks instead of two (workgroups of 256 output channels, Cout % 256
+// == 0: the x tile is staged and split once per 256 channels and every pair of LDS reads feeds 12 MFMAs), and the two
+// planes may be double-buffered (stage s + 1 is split and written while other waves still run stage s's MFMAs: one
+// barrier per stage instead of two, 69632 B of LDS, still two workgroups per CU).
 #include "common.h"
 
 namespace ys {
@@ -43,15 +49,16 @@ struct Args {
 };
 
 // NP pixels per tile (64 or 128: the weights are read from L2 once per tile, 128 halves that traffic)
-// CPW: 16-channel output blocks per wave (2: workgroups of 128 output channels; 1: of 64, for Cout 64)
-template <bool DUAL, int NP, int CPW = 2>
+// CPW: 16-channel output blocks per wave (2: workgroups of 128 output channels; 4: of 256; 1: of 64, for Cout 64)
+// DB: the staged planes are double-buffered (one barrier per stage)
+template <bool DUAL, int NP, int CPW = 2, bool DB = false>
 __global__ __launch_bounds__(NT, 2) void conv1x1_x2_kernel(Args p) {
   constexpr int PL = NP * PS;           // plane (halves)
   constexpr int NITEM = (KS / 4) * NP;  // (channel quad, pixel) items per stage
   constexpr int NIT = NITEM / NT;
   constexpr int NPB = NP / 16;          // pixel blocks
   static_assert(NITEM % NT == 0, "items");
-  __shared__ __attribute__((aligned(16))) h16_t Pl[2 * PL];
+  __shared__ __attribute__((aligned(16))) h16_t Pl[(DB ? 4 : 2) * PL];
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, g = lane >> 4;
   const int ngrp = p.cout / (64 * CPW);
@@ -118,20 +125,32 @@ __global__ __launch_bounds__(NT, 2) void conv1x1_x2_kernel(Args p) {
 #pragma unroll
   for (int u = 0; u < CPW; ++u) bo[u] = p.bias[16 * (cb0 + u) + l15];
 
-  load_part(0, 0, 4 * NIT, true);
-  for (int st = 0; st < nst; ++st) {
-    __syncthreads();  // every wave is done with the previous stage's planes
+  // the loaded stage, split, as the two planes at pl
+  auto stage_store = [&](h16_t* pl) __attribute__((always_inline)) {
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
       const int e = tid + NT * i, quad = e / NP, px = e - quad * NP;
       uint2 hh, ll;
       split4x(sv[i], hh, ll);
       rng = range_acc(rng, sv[i]);
-      h16_t* d = Pl + px * PS + 4 * quad;
+      h16_t* d = pl + px * PS + 4 * quad;
       *reinterpret_cast<uint2*>(d) = hh;
       *reinterpret_cast<uint2*>(d + PL) = ll;
     }
+  };
+  load_part(0, 0, 4 * NIT, true);
+  if (DB) {
+    stage_store(Pl);
     __syncthreads();
+  }
+  for (int st = 0; st < nst; ++st) {
+    // DB: stage st is in plane pair st & 1 (written during stage st - 1, behind that stage's barrier)
+    const h16_t* cur = DB ? Pl + (st & 1) * 2 * PL : Pl;
+    if (!DB) {
+      __syncthreads();  // every wave is done with the previous stage's planes
+      stage_store(Pl);
+      __syncthreads();
+    }
     const bool nlive = st + 1 < nst;
     const int stn = nlive ? st + 1 : st;
     f16x8_t wa[CPW][2], wn[CPW][2];
@@ -153,7 +172,7 @@ __global__ __launch_bounds__(NT, 2) void conv1x1_x2_kernel(Args p) {
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int k = 0; k < NPB; ++k) {
-        const h16_t* src = Pl + (16 * k + l15) * PS + 32 * kk + 8 * g;
+        const h16_t* src = cur + (16 * k + l15) * PS + 32 * kk + 8 * g;
         const f16x8_t xh = *reinterpret_cast<const f16x8_t*>(src);
         const f16x8_t xl = *reinterpret_cast<const f16x8_t*>(src + PL);
 #pragma unroll
@@ -168,6 +187,12 @@ __global__ __launch_bounds__(NT, 2) void conv1x1_x2_kernel(Args p) {
         wa[u][0] = wn[u][0];
         wa[u][1] = wn[u][1];
       }
+    }
+    if (DB && nlive) {
+      // the other pair's last readers were stage st - 1's MFMAs, all done before the barrier that ended that stage;
+      // this barrier publishes stage st + 1 and ends the reads of stage st's pair, which stage st + 1 overwrites
+      stage_store(Pl + ((st + 1) & 1) * 2 * PL);
+      __syncthreads();
     }
   }
   // epilogue: lane (g, l15) of (u, pixel block k) holds channel 16 (cb0 + u) + l15, pixels 16 k + 4 g .. + 3
@@ -219,6 +244,58 @@ __global__ __launch_bounds__(256) void conv1x1_prep_kernel(const float* __restri
 using namespace ys;
 
 static int c1_pad(int cin) { return (cin + c1::KS - 1) / c1::KS * c1::KS; }
+
+// Forced form of the kernel (tests / per-shape measurements compare forms; the automatic choice is the product):
+// form = groups + 4 buffers; groups 0 automatic, 1 workgroups of 128 output channels, 2 of 256 (Cout % 256 == 0; any
+// other Cout runs 1); buffers 0 automatic, 1 one pair of staged planes, 2 two pairs (double-buffered). Cout 64 has one
+// form (64-channel workgroups, one pair), reported as 1 + 4 * 1. Returns the previous value.
+static int g_c1_form = 0;
+YS_EXPORT int yolosod_debug_set_conv1x1x2_form(int form) {
+  const int old = g_c1_form;
+  if (form >= 0 && form < 12 && (form & 3) != 3) g_c1_form = form;
+  return old;
+}
+
+static int c1_cu_count() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0, c = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0)
+      c = 256;
+    n = c;
+  }
+  return n;
+}
+
+// The resolved form (groups 1 .. 2 + 4 * buffers 1 .. 2) of a launch: the forced fields of g_c1_form, the automatic
+// choice for the others. Automatic (scripts/bench_conv1x1x2.py forms, batch 32, each library twice):
+// 256-channel groups for Cout 512 on maps of at most 20 x 20 when the 128-channel items would not fit the workgroup
+// slots (two per CU) in one round - 512 / 768 / 1024 -> 512 at 20^2 run 0.004 - 0.005 ms shorter, more than the
+// 0.0035 ms between two runs of one build; at Cout 256 and at 40^2 no form beat the old one by that, and the
+// double-buffered forms did nowhere on every shape of a class, so they are forms to force only.
+static int c1_form(int B, int cout, int HW) {
+  if (cout == 64) return 1 + 4 * 1;
+  const int fgrp = g_c1_form & 3, fbuf = g_c1_form >> 2;
+  const bool g256 = fgrp ? fgrp == 2
+                         : cout == 512 && HW <= 400 && (long)B * ((HW + 63) / 64) * (cout / 128) > 2L * c1_cu_count();
+  return (g256 && cout % 256 == 0 ? 2 : 1) + 4 * (fbuf ? fbuf : 1);
+}
+
+// The form (as yolosod_debug_set_conv1x1x2_form encodes it, no field 0) a [B][*][H][W] -> cout launch runs in under
+// the current setting; 0 for shapes the kernel does not take.
+YS_EXPORT int yolosod_debug_conv1x1x2_form(int B, int cout, int H, int W) {
+  if (B <= 0 || H <= 0 || W <= 0 || ((long)H * W) % 4 || cout <= 0 || (cout != 64 && cout % 128) || cout > 1024)
+    return 0;
+  return c1_form(B, cout, H * W);
+}
+
+// the 64-pixel-tile instance <dual, 64, CPW, DB> (yolosod_conv1x1x2_silu_cat's NPx)
+template <int CPW, bool DB>
+static void c1_launch(bool dual, unsigned nwg, hipStream_t st, const c1::Args& a) {
+  if (dual) hipLaunchKernelGGL((c1::conv1x1_x2_kernel<true, 64, CPW, DB>), dim3(nwg), dim3(c1::NT), 0, st, a);
+  else hipLaunchKernelGGL((c1::conv1x1_x2_kernel<false, 64, CPW, DB>), dim3(nwg), dim3(c1::NT), 0, st, a);
+}
 
 // Cout 64 or a multiple of 128 (<= 1024), Cin a multiple of 32 (<= 4096; the weights are padded to a multiple of 128)
 YS_EXPORT size_t yolosod_conv1x1x2_prep_bytes(int cin, int cout) {
@@ -291,16 +368,16 @@ YS_EXPORT int yolosod_conv1x1x2_silu_cat(const float* x, long x_bstride, const f
   const int ntile = (HW + NPx - 1) / NPx;
   c1::Args a{x, x_bstride, wp, bias, y, y_bstride, y2, y2_bstride, c2lo, cin, cout, HW, ntile, range_flag_dev(), flag,
              x2, x2_bstride, k1, up_w};
-  const long nwg = (long)B * ntile * (cout == 64 ? 1 : cout / 128);
+  const int form = c1_form(B, cout, HW);
+  const bool g256 = (form & 3) == 2, db = (form >> 2) == 2;
+  const long nwg = (long)B * ntile * (cout == 64 ? 1 : cout / (g256 ? 256 : 128));
   YS_CHECK_ARG(nwg < (1L << 31), "conv1x1x2: too many tiles");
   hipStream_t st = (hipStream_t)stream;
-  if (cout == 64) {  // one 64-channel group: a 16-channel block per wave
-    if (y2) hipLaunchKernelGGL((c1::conv1x1_x2_kernel<true, 64, 1>), dim3((unsigned)nwg), dim3(c1::NT), 0, st, a);
-    else hipLaunchKernelGGL((c1::conv1x1_x2_kernel<false, 64, 1>), dim3((unsigned)nwg), dim3(c1::NT), 0, st, a);
-  } else {
-    if (y2) hipLaunchKernelGGL((c1::conv1x1_x2_kernel<true, NPx>), dim3((unsigned)nwg), dim3(c1::NT), 0, st, a);
-    else hipLaunchKernelGGL((c1::conv1x1_x2_kernel<false, NPx>), dim3((unsigned)nwg), dim3(c1::NT), 0, st, a);
-  }
+  if (cout == 64) c1_launch<1, false>(y2 != nullptr, (unsigned)nwg, st, a);  // a 16-channel block per wave
+  else if (g256 && db) c1_launch<4, true>(y2 != nullptr, (unsigned)nwg, st, a);
+  else if (g256) c1_launch<4, false>(y2 != nullptr, (unsigned)nwg, st, a);
+  else if (db) c1_launch<2, true>(y2 != nullptr, (unsigned)nwg, st, a);
+  else c1_launch<2, false>(y2 != nullptr, (unsigned)nwg, st, a);
   YS_CHECK_LAUNCH("conv1x1x2");
   return 0;
 }

@@ -142,6 +142,8 @@ S2_NECK = os.environ.get("YOLOSOD_S2_NECK", "1") != "0"
 #   on   {10}    0.128          8 of 8           7.838 - 7.864   (the defaults now)
 #   on   all     0.116          9: fails         -               
 # The unedited tests are the bar; among the configurations that pass them, the fastest ships.
+# The backbone's wide 1x1 convs have a switch of the same kind (N1_BACKBONE below), chosen by the same bar
+# with these two defaults in place.
 S1_BACKBONE_DEFAULT, S2_BACKBONE_DEFAULT = "1", "10"
 S2_BACKBONE_LAYERS = (7, 10)
 
@@ -171,6 +173,24 @@ S1_NECK = os.environ.get("YOLOSOD_S1_NECK", "1") != "0"
 # the PAN neck's wide 1x1 convs (Cout a multiple of 128: C2f cv1 / cv2, lateral convs) on the fp16-split 1x1 kernel
 # (csrc/conv1x1x2.hip) with bias / SiLU / concat slice / C2f's dual store in its epilogue; YOLOSOD_N1_NECK=0: MIOpen
 N1_NECK = os.environ.get("YOLOSOD_N1_NECK", "1") != "0"
+# the backbone's wide 1x1 convs (Cout a multiple of 128: cv1 / cv2 of the C2fs L6 / L8 / L11 and of SPPF L13, eight
+# convs at the paper scale) on the same kernel instead of MIOpen's fp32 GEMM + the bias / SiLU pass, C2f cv1 and SPPF
+# cv1 into their slice of the concat buffer. YOLOSOD_N1_BACKBONE = 0 / 1 / a comma list of those layers.
+# False, True or a frozenset of layer indices, as S2_BACKBONE.
+# Default: layers 8 / 11 / 13. The same bar as above, tests/test_gpu_e2e.py unedited, one box, S2 {10}:
+#   N1           noisy worst box px (bound 0.158)   recall |d| (bound 1e-3)   test     ms per step
+#   none         0.128                               -                         passes   8.09
+#   all          0.159                               1.07e-3                   fails    (7.58)
+#   all, S2 none 0.156                               1.07e-3                   fails    -
+#   {8,11,13}    0.143                               -                         passes   7.54
+#   {6,11,13}    0.183                               -                         fails    -
+#   {6,8,13}     0.175                               -                         fails    -
+#   {6,8,11}     0.160                               1.07e-3                   fails    -
+# Every configuration with layer 6 fails; layer 6 (80^2 maps, Cin 128 / 256) is also where the kernel gains nothing
+# over MIOpen + the epilogue pass.
+N1_BACKBONE_DEFAULT = "8,11,13"
+N1_BACKBONE_LAYERS = (6, 8, 11, 13)
+N1_BACKBONE = _backbone_switch(os.environ.get("YOLOSOD_N1_BACKBONE", N1_BACKBONE_DEFAULT), N1_BACKBONE_LAYERS)
 # the neck C2fs' Bottlenecks (stride-1 fp16-split kernel) read their inputs as slices of the C2f buffer instead of
 # packed copies written by a second store (YOLOSOD_C2F_SLICES=0: the dual-store form)
 C2F_SLICES = os.environ.get("YOLOSOD_C2F_SLICES", "1") != "0"
@@ -201,6 +221,26 @@ def _s1_on(s1) -> bool:
     return bool(s1) and (S1_BACKBONE if s1 == "backbone" else S1_NECK)
 
 
+def _n1_on(n1, layer=None):
+    """Whether a Conv's wide-1x1 mark (False / True: neck / "backbone") routes it to the fp16-split 1x1 kernel.
+    N1_BACKBONE is False, True or a frozenset of layer indices; ``layer`` is the index of the backbone layer the conv
+    belongs to (Conv.n1_layer)."""
+    if not n1:
+        return False
+    if n1 != "backbone":
+        return N1_NECK
+    if layer is None or isinstance(N1_BACKBONE, bool):
+        return bool(N1_BACKBONE)
+    return layer in N1_BACKBONE
+
+
+def _n1_run(conv, x, out, out2, c2lo, n1):
+    """The fp16-split 1x1 kernel on a conv that conv_epilogue routed to it."""
+    prep = lambda: _cached(conv, "c1prep", (conv.weight,), lambda: _hip.conv1x1x2_prepare(conv.weight))  # noqa: E731
+    return _hip.conv1x1x2_silu(x, conv.bias, prep, conv.out_channels, out=out, out2=out2, c2lo=c2lo,
+                               op="conv1x1x2_backbone" if n1 == "backbone" else "conv1x1x2")
+
+
 def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, out2=None, c2lo=0, tower=False,
                   s2=False, s1=False, n1=False, layer=None):
     """GPU fast path of ``act(conv(x)) (+ res)``: MIOpen conv without bias, then one HIP pass for bias +
@@ -214,7 +254,8 @@ def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, 
     conv's index in the model).
     ``s1``: one of the C2f Bottleneck 3x3 convs (the stride-1 fp16-split kernel, with out / res): True for the neck's
     (S1_NECK), "backbone" for the backbone's (S1_BACKBONE).
-    ``n1``: one of the neck's wide 1x1 convs (the fp16-split 1x1 kernel, with out / out2).
+    ``n1``: one of the wide 1x1 convs (the fp16-split 1x1 kernel, with out / out2): True for the neck's (N1_NECK),
+    "backbone" for the backbone's (N1_BACKBONE, which may name layers: ``layer`` is the index of the conv's layer).
     Returns None when the fast path does not apply (CPU tensor, no bias, unsupported activation / shape)."""
     if x.device.type != "cuda" or conv.bias is None or act_code is None or x.dtype not in (torch.float32,
                                                                                            torch.bfloat16):
@@ -222,10 +263,9 @@ def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, 
     split = _hip.split_convs_enabled()  # false inside _hip.exact_fp32_matrix(): no fp16-split conv kernel
     if isinstance(x, _hip.CatView):  # a virtual concat: a 1x1 kernel reads both parts in place, else materialise
         if act_code == 1 and res is None and stats is None and conv.kernel_size == (1, 1):
-            if split and n1 and N1_NECK and _hip.conv1x1x2_ok(x, conv) and (out is None or _hip._imgs_contig(out)) and (
-                    out2 is None or _hip._imgs_contig(out2)):
-                prep = lambda: _cached(conv, "c1prep", (conv.weight,), lambda: _hip.conv1x1x2_prepare(conv.weight))  # noqa: E731
-                return _hip.conv1x1x2_silu(x, conv.bias, prep, conv.out_channels, out=out, out2=out2, c2lo=c2lo)
+            if split and _n1_on(n1, layer) and _hip.conv1x1x2_ok(x, conv) and (
+                    out is None or _hip._imgs_contig(out)) and (out2 is None or _hip._imgs_contig(out2)):
+                return _n1_run(conv, x, out, out2, c2lo, n1)
             if (THIN1X1 and conv.out_channels == 64 and conv.stride == (1, 1) and conv.groups == 1
                     and conv.padding == (0, 0) and _hip.conv1x1_thin_ok(x, conv.out_channels)
                     and (out is None or out.data_ptr() % 16 == 0)):
@@ -236,10 +276,10 @@ def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, 
             and (CONV3X3 == "all" or tower) and _hip.conv3x3_ok(x, conv)):
         prep = lambda: _cached(conv, "c3prep", (conv.weight,), lambda: _hip.conv3x3_prepare(conv.weight))  # noqa: E731
         return _hip.conv3x3_silu(x, conv.bias, prep, conv.out_channels)
-    if (split and n1 and N1_NECK and act_code == 1 and res is None and stats is None and _hip.conv1x1x2_ok(x, conv)
-            and (out is None or _hip._imgs_contig(out)) and (out2 is None or _hip._imgs_contig(out2))):
-        prep = lambda: _cached(conv, "c1prep", (conv.weight,), lambda: _hip.conv1x1x2_prepare(conv.weight))  # noqa: E731
-        return _hip.conv1x1x2_silu(x, conv.bias, prep, conv.out_channels, out=out, out2=out2, c2lo=c2lo)
+    if (split and _n1_on(n1, layer) and act_code == 1 and res is None and stats is None
+            and _hip.conv1x1x2_ok(x, conv) and (out is None or _hip._imgs_contig(out))
+            and (out2 is None or _hip._imgs_contig(out2))):
+        return _n1_run(conv, x, out, out2, c2lo, n1)
     if (split and _s1_on(s1) and act_code == 1 and stats is None and out2 is None and _hip.conv3x3_ok(x, conv)
             and x.shape[3] % 4 == 0 and (res is None or _hip._imgs_contig(res))):
         prep = lambda: _cached(conv, "c3prep", (conv.weight,), lambda: _hip.conv3x3_prepare(conv.weight))  # noqa: E731
@@ -310,6 +350,12 @@ class Conv(nn.Module):
     s1_backbone = False
     # set by DetectionModel on the neck's wide 1x1 convs: the fp16-split 1x1 kernel runs them (N1_NECK)
     n1 = False
+    # set by DetectionModel on the backbone's wide 1x1 convs (C2f / SPPF cv1 and cv2): the same kernel runs them
+    # (N1_BACKBONE, which may name layers). ``n1`` stays False on them
+    n1_backbone = False
+    # the index in DetectionModel.model of the C2f / SPPF an n1_backbone conv belongs to, handed to conv_epilogue as
+    # its ``layer`` (``layer`` itself stays the stride-2 convs': a conv carries at most one of the two marks)
+    n1_layer = None
     # set by DetectionModel on layer 0 when it is a 3-channel 3x3 / stride-2 Conv feeding an SE: the stem kernel (STEM_HIP)
     stem = False
 
@@ -339,7 +385,9 @@ class Conv(nn.Module):
                 and isinstance(self.act, nn.SiLU) and _hip.stem_ok(x, self.conv)):
             return _hip.stem_conv(x, self.conv.weight.detach(), self.conv.bias.detach())
         y = conv_epilogue(self.conv, _act_code(self.act), x, out, res, self.emit_stats, out2, c2lo, self.tower,
-                          "backbone" if self.s2_backbone else self.s2, self.s1_mark(), self.n1, self.layer)
+                          "backbone" if self.s2_backbone else self.s2, self.s1_mark(),
+                          "backbone" if self.n1_backbone else self.n1,
+                          self.n1_layer if self.n1_backbone else self.layer)
         if y is not None:
             return y
         if isinstance(x, _hip.CatView):

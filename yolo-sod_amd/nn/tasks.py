@@ -488,6 +488,12 @@ class DetectionModel(BaseModel):
                            [m.cv1, m.cv2] if isinstance(m, M.C2f) else []):
                     if cv.conv.kernel_size == (1, 1) and cv.conv.groups == 1 and cv.conv.out_channels % 128 == 0:
                         cv.n1 = True
+            # the backbone's wide 1x1 convs (modules.N1_BACKBONE, which may name layers): cv1 / cv2 of C2f and SPPF
+            elif isinstance(m, (M.C2f, M.SPPF)):
+                for cv in (m.cv1, m.cv2):
+                    if cv.conv.kernel_size == (1, 1) and cv.conv.groups == 1 and cv.conv.out_channels % 128 == 0:
+                        cv.n1_backbone = True
+                        cv.n1_layer = i
 
         # lazy SE weights: the reference creates them during the stride probe, in forward (= layer) order,
         # after every eager module -> same RNG stream position here.
