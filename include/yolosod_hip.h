@@ -221,6 +221,26 @@ int yolosod_scale_boxes(float* det, const int* counts, int B, int D, const float
  * 1..65535; 16-byte accesses when A % 4 == 0 and y, merged are 16-byte aligned. */
 int yolosod_tile_merge(const float* y, int n, int nc, int A, const int32_t* desc, int rows, float* merged, int F,
                        int S, float cut_margin, void* stream);
+/* Test-time augmentation   ultralytics/nn/tasks.py:381-418 (_predict_augment), utils/torch_utils.py:423-432 (scale_img)
+ * (csrc/tta.hip). yolosod_tta_views makes every scaled / flipped view of one batch in one launch. x: [B][C][H][W]
+ * contiguous, fp32 or (bf16) bf16 bit patterns. desc: device int64 [V][8] = output address, flip (0 none, 2 up-down,
+ * 3 left-right), sh, sw (resized size), ph, pw (padded size), 0, 0; view v is [B][C][ph][pw] contiguous in x's type at
+ * its address, 16-byte aligned, pw % 4 == 0, sh <= ph <= max_ph, sw <= pw <= max_pw (the launch is sized by max_ph x
+ * max_pw; a row that breaks this writes nothing). Every element of every view is written exactly once: the flipped x
+ * resized to sh x sw at the top-left, 0.447f elsewhere. Resize per axis n_in -> n_out in fp32, every operation rounded
+ * on its own: scale = float(n_in) / float(n_out); src = max(scale * (d + 0.5f) - 0.5f, 0); i0 = min((int)src,
+ * n_in - 1); i1 = i0 + (i0 < n_in - 1); l1 = src - i0; l0 = 1 - l1; a flip replaces index i by n_in - 1 - i on its
+ * axis; value = ly0 * (lx0 * a + lx1 * b) + ly1 * (lx0 * c + lx1 * d). bf16 input is widened first, the fp32 value is
+ * rounded once to nearest even. Upscaling included. V * B * C <= 65535, extents <= 16384. Deterministic.
+ * yolosod_tta_merge is _descale_pred + _clip_augmented + torch.cat for one branch: anchors [src_lo, src_lo + n) of
+ * y [B][4+nc][A] (fp32, the head's output for the view) become anchors [dst, dst + n) of cat [B][4+nc][A_tot]: x, y, w,
+ * h each / scale (IEEE division), then x = img_w - x (flip 3) or y = img_h - y (flip 2); scores are copied. Everything
+ * in the named range is written exactly once, nothing else is touched, no atomics. nc in 1..64, B <= 65535, scale
+ * finite and > 0, the ranges inside y and cat. */
+int yolosod_tta_views(const void* x, int B, int C, int H, int W, int bf16, const int64_t* desc, int V, int max_ph,
+                      int max_pw, void* stream);
+int yolosod_tta_merge(const float* y, int B, int nc, int A, int src_lo, int n, float* cat, int A_tot, int dst,
+                      float scale, int flip, float img_w, float img_h, void* stream);
 /* BaseValidator.match_predictions over box_iou   ultralytics/engine/validator.py:222-262 (greedy path),
  * ultralytics/utils/metrics.py:52-71, for a whole batch of padded NMS rows in one launch, no host sync
  * (csrc/eval_match.hip). det: [B][D][6] padded NMS rows (x1, y1, x2, y2, conf, cls), counts: device [B]. labels:

@@ -57,6 +57,8 @@ SIGNATURES = {
     "yolosod_scale_boxes": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "yolosod_tile_merge": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _f, _vp]),
     "yolosod_match_predictions": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "yolosod_tta_views": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
+    "yolosod_tta_merge": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _i, _f, _f, _vp]),
     "yolosod_stem_workspace": (_sz, [_i, _i, _i, _i]),
     "yolosod_stem_conv": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _l, _vp, _vp, _sz, _vp]),
     "yolosod_conv1x1_thin_stats": (_i, [_vp, _l, _vp, _vp, _vp, _l, _i, _i, _i, _l, _i, _vp, _vp, _vp, _vp]),
@@ -1244,6 +1246,129 @@ def tile_merge(y, rows, merged, A, cut_margin=None):
     _check(_launch(("tile_merge", (n, no, A), (F, S)), dev, lib.yolosod_tile_merge, y.data_ptr(), n, nc, A,
                    d.data_ptr(), len(rows), merged.data_ptr(), F, S, cm, _stream(dev)), "tile_merge")
     return merged
+
+
+TTA_MAX_DIM = 16384  # extents of csrc/tta.hip
+TTA_MAX_NC = 64
+TTA_FLIPS = {None: 0, 0: 0, 2: 2, 3: 3}  # the reference's codes: 2 up-down, 3 left-right
+
+
+def tta_views(x, views, outs=None, cache=None):
+    """Every scaled / flipped view of a batch in one launch (torch.ops.yolosod.tta_views, yolosod_tta_views): ``x``
+    [B, C, H, W] contiguous, float32 or bfloat16, on the GPU; ``views`` a sequence of ``(flip, sh, sw, ph, pw)``
+    (``TTAPlan.views``): flip None / 2 (up-down) / 3 (left-right), the resized size and the padded size (pw % 4 == 0).
+    Returns the list of views, [B, C, ph, pw] each in x's dtype: x flipped and resized (bilinear, csrc/tta.hip) at the
+    top-left, 0.447 elsewhere. ``outs``: write into these tensors instead (contiguous, 16-byte aligned); otherwise all
+    views are carved from one allocation. ``cache``: a dict that keeps the uploaded descriptor table per output
+    addresses (the caching allocator hands a steady-state loop the same block: no upload then).
+
+    The table the kernel reads is built here from the tensors' own ``data_ptr()`` and goes up as one pinned
+    non-blocking copy; everything the kernel relies on is checked here first: nothing is launched on arguments that
+    fail."""
+    if not isinstance(x, torch.Tensor):
+        raise TypeError("tta_views: x: expected a tensor")
+    if x.device.type != "cuda":
+        raise RuntimeError(f"tta_views: x: HIP kernel requires GPU tensors (got device {x.device}); no CPU fallback")
+    if x.dtype not in (torch.float32, _BF16):
+        raise RuntimeError(f"tta_views: x must be float32 or bfloat16, got {x.dtype}")
+    if x.dim() != 4:
+        raise RuntimeError(f"tta_views: x: expected [B, C, H, W], got shape {tuple(x.shape)}")
+    if not x.is_contiguous():
+        raise RuntimeError("tta_views: x: expected a contiguous tensor")
+    B, C, H, W = (int(v) for v in x.shape)
+    if B < 1 or C < 1 or not (0 < H <= TTA_MAX_DIM and 0 < W <= TTA_MAX_DIM):
+        raise RuntimeError(f"tta_views: x {tuple(x.shape)} unsupported (extents 1..{TTA_MAX_DIM})")
+    views = list(views)
+    V = len(views)
+    if V < 1 or V * B * C > 65535:
+        raise RuntimeError(f"tta_views: {V} views of {B} x {C} planes (1 <= views * B * C <= 65535)")
+    geom = []
+    for i, v in enumerate(views):
+        if len(v) != 5 or v[0] not in TTA_FLIPS:
+            raise RuntimeError(f"tta_views: view {i}: expected (flip None / 2 / 3, sh, sw, ph, pw), got {tuple(v)}")
+        sh, sw, ph, pw = (int(k) for k in v[1:])
+        if pw % 4:
+            raise RuntimeError(f"tta_views: view {i}: padded width {pw} is no multiple of 4")
+        if not (1 <= sh <= ph <= TTA_MAX_DIM and 1 <= sw <= pw <= TTA_MAX_DIM):
+            raise RuntimeError(f"tta_views: view {i}: {sh}x{sw} in {ph}x{pw} unsupported (1 <= resized <= padded <= "
+                               f"{TTA_MAX_DIM})")
+        geom.append((TTA_FLIPS[v[0]], sh, sw, ph, pw))
+    dev = x.device
+    if outs is None:
+        item = x.element_size()
+        sizes = [(B * C * g[3] * g[4] * item + 15) // 16 * 16 for g in geom]
+        buf = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
+        outs, o = [], 0
+        for g, n in zip(geom, sizes):
+            outs.append(buf[o:o + B * C * g[3] * g[4] * item].view(x.dtype).view(B, C, g[3], g[4]))
+            o += n
+    else:
+        outs = list(outs)
+        if len(outs) != V:
+            raise RuntimeError(f"tta_views: {len(outs)} outputs for {V} views")
+        for i, (t, g) in enumerate(zip(outs, geom)):
+            if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != x.dtype
+                    or tuple(t.shape) != (B, C, g[3], g[4]) or not t.is_contiguous() or t.data_ptr() % 16):
+                raise RuntimeError(f"tta_views: view {i}: out must be a contiguous 16-byte aligned {x.dtype} "
+                                   f"[{B}, {C}, {g[3]}, {g[4]}] tensor on {dev}")
+    key = (str(dev), tuple(t.data_ptr() for t in outs), tuple(geom))
+    desc = None if cache is None else cache.get(key)
+    if desc is None:
+        rows = [[t.data_ptr(), *g, 0, 0] for t, g in zip(outs, geom)]
+        desc = torch.tensor(rows, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+        if cache is not None:
+            if len(cache) >= 64:
+                cache.clear()
+            cache[key] = desc
+    _launch(("tta_views", tuple(x.shape), tuple(geom)) + ((2,) if x.dtype == _BF16 else ()), dev, ops().tta_views, x,
+            desc, outs, [k for g in geom for k in g])
+    return outs
+
+
+def tta_merge(y, cat, src_lo, n, dst, scale, flip, img_hw):
+    """One branch of augmented inference into the concatenated prediction tensor, one launch
+    (torch.ops.yolosod.tta_merge, yolosod_tta_merge; the reference's ``_descale_pred`` + ``_clip_augmented`` +
+    ``torch.cat``): anchors [src_lo, src_lo + n) of ``y`` [B, 4+nc, A] fp32 (the head's output for the view) become
+    anchors [dst, dst + n) of ``cat`` [B, 4+nc, A_tot] fp32: xywh / float32(scale), then x = img_w - x (flip 3) or
+    y = img_h - y (flip 2); scores are copied. Nothing else of ``cat`` is touched. Returns ``cat``. Everything the
+    kernel relies on is checked here first: nothing is launched on arguments that fail."""
+    for t, name in ((y, "y"), (cat, "cat")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"tta_merge: {name}: expected a tensor")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"tta_merge: {name}: HIP kernel requires GPU tensors (got device {t.device}); "
+                               "no CPU fallback")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"tta_merge: {name}: expected float32, got {t.dtype}")
+        if t.dim() != 3:
+            raise RuntimeError(f"tta_merge: {name}: expected 3 dimensions, got shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"tta_merge: {name}: expected a contiguous tensor")
+    if cat.device != y.device:
+        raise RuntimeError(f"tta_merge: y on {y.device}, cat on {cat.device}")
+    B, no, A = (int(v) for v in y.shape)
+    nc = no - 4
+    if B < 1 or B > 65535 or A < 1 or not 1 <= nc <= TTA_MAX_NC:
+        raise RuntimeError(f"tta_merge: y {tuple(y.shape)} unsupported (B 1..65535, 1..{TTA_MAX_NC} classes)")
+    A_tot = int(cat.shape[2])
+    if int(cat.shape[0]) != B or int(cat.shape[1]) != no:
+        raise RuntimeError(f"tta_merge: cat {tuple(cat.shape)} is not [{B}, {no}, A_tot]")
+    if max(A, A_tot) * no >= 1 << 31:
+        raise RuntimeError(f"tta_merge: A * (4 + nc) >= 2^31")
+    src_lo, n, dst = int(src_lo), int(n), int(dst)
+    if n < 1 or src_lo < 0 or src_lo + n > A:
+        raise RuntimeError(f"tta_merge: source anchors [{src_lo}, {src_lo + n}) leave y's {A}")
+    if dst < 0 or dst + n > A_tot:
+        raise RuntimeError(f"tta_merge: destination anchors [{dst}, {dst + n}) leave cat's {A_tot}")
+    scale = float(scale)
+    if not (scale > 0.0 and scale < float("inf")):
+        raise RuntimeError(f"tta_merge: scale {scale} (finite and > 0 expected)")
+    if flip not in TTA_FLIPS:
+        raise RuntimeError(f"tta_merge: flip {flip} (None, 2 or 3)")
+    img_h, img_w = int(img_hw[0]), int(img_hw[1])
+    _launch(("tta_merge", (B, no, n), (A, A_tot)), y.device, ops().tta_merge, y, cat, src_lo, n, dst, scale,
+            TTA_FLIPS[flip], img_h, img_w)
+    return cat
 
 
 EVAL_MATCH_LABEL_CHUNK = 256  # labels staged through LDS per pass (csrc/eval_match.hip ematch::CHUNK)

@@ -20,7 +20,9 @@ ARCH = os.environ.get("YOLOSOD_ARCH", "gfx950")
 # per-file extra flags: the decode / NMS / tile-merge arithmetic must not be contracted into FMAs (bit-exact NMS
 # indices; the merged boxes are NMS's input), nor the evaluator's box_iou (bit-exact true-positive matrix)
 EXTRA = {"detect.hip": ["-ffp-contract=off"], "nms.hip": ["-ffp-contract=off"],
-         "tile_merge.hip": ["-ffp-contract=off"], "eval_match.hip": ["-ffp-contract=off"]}
+         "tile_merge.hip": ["-ffp-contract=off"], "eval_match.hip": ["-ffp-contract=off"],
+         # the augmented views' bilinear blend and the branch merge: every product and sum rounds on its own
+         "tta.hip": ["-ffp-contract=off"]}
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-variable",
           "-Wno-unused-function", f"-I{INCLUDE}", f"-I{CSRC}"]
 

@@ -1,6 +1,6 @@
 // Torch-op registration of the hot-path kernel families ("a torch.utils.cpp_extension module ... thin
 // wrappers registered as torch ops"): torch.ops.yolosod.{se_fwd, cbam_fwd, ca_fwd, a2_fwd, swin_fwd,
-// detect_head_fwd, detect_decode_fwd, nms_batched}.
+// detect_head_fwd, detect_decode_fwd, nms_batched, stem_fwd, tta_views, tta_merge}.
 //
 // Each op validates its tensors with TORCH_CHECK (RuntimeError in Python, as the reference's own asserts /
 // exceptions surface, e.g. a2_attn.py:24), allocates its output and workspace with at::empty on the input's device
@@ -447,6 +447,55 @@ std::tuple<Tensor, Tensor> stem_fwd(const Tensor& x, const Tensor& weight, const
   return {out, psum};
 }
 
+// Test-time augmentation (csrc/tta.hip). tta_views: every view of x into outs[v] ([B, C, ph, pw] of x's type) in one
+// launch; desc is the device int64 [V][8] table that names outs' addresses and geom = (flip, sh, sw, ph, pw) per view
+// the same sizes on the host (_hip.tta_views builds both; outs are checked against geom here).
+void tta_views(const Tensor& x, const Tensor& desc, at::TensorList outs, at::IntArrayRef geom) {
+  const bool bf = act_bf16(x, "tta_views");
+  const int64_t V = outs.size();
+  TORCH_CHECK(V >= 1 && (int64_t)geom.size() == 5 * V, "tta_views: ", V, " outputs with ", geom.size(), " geometry values");
+  TORCH_CHECK(desc.device() == x.device() && desc.scalar_type() == at::kLong && desc.is_contiguous() &&
+                  desc.numel() == 8 * V, "tta_views: desc must be a contiguous int64 [", V, ", 8] tensor on x's device");
+  int64_t max_ph = 0, max_pw = 0;
+  for (int64_t v = 0; v < V; ++v) {
+    const int64_t flip = geom[5 * v], sh = geom[5 * v + 1], sw = geom[5 * v + 2], ph = geom[5 * v + 3], pw = geom[5 * v + 4];
+    TORCH_CHECK((flip == 0 || flip == 2 || flip == 3) && sh >= 1 && sw >= 1 && sh <= ph && sw <= pw && pw % 4 == 0,
+                "tta_views: view ", v, ": flip ", flip, ", ", sh, "x", sw, " in ", ph, "x", pw, " unsupported");
+    const Tensor& o = outs[v];
+    TORCH_CHECK(o.device() == x.device() && o.scalar_type() == x.scalar_type() && o.is_contiguous() && o.dim() == 4 &&
+                    o.size(0) == x.size(0) && o.size(1) == x.size(1) && o.size(2) == ph && o.size(3) == pw &&
+                    (uintptr_t)o.data_ptr() % 16 == 0,
+                "tta_views: view ", v, ": output must be a contiguous 16-byte aligned [B, C, ", ph, ", ", pw, "] tensor");
+    max_ph = std::max(max_ph, ph);
+    max_pw = std::max(max_pw, pw);
+  }
+  c10::DeviceGuard guard(x.device());
+  auto st = c10::hip::getCurrentHIPStream(x.get_device());
+  check_rc(yolosod_tta_views(x.data_ptr(), x.size(0), x.size(1), x.size(2), x.size(3), bf ? 1 : 0,
+                             (const int64_t*)desc.data_ptr(), (int)V, (int)max_ph, (int)max_pw, sp(st)),
+           "tta_views");
+}
+
+// tta_merge: anchors [src_lo, src_lo + n) of y [B, 4+nc, A] de-scaled / de-flipped into anchors [dst, dst + n) of cat
+void tta_merge(const Tensor& y, Tensor& cat, int64_t src_lo, int64_t n, int64_t dst, double scale, int64_t flip,
+               int64_t img_h, int64_t img_w) {
+  for (const Tensor* t : {&y, (const Tensor*)&cat}) {
+    TORCH_CHECK(t->is_cuda(), "tta_merge: HIP kernel requires a GPU tensor (got ", t->device(), "); no CPU fallback");
+    TORCH_CHECK(t->scalar_type() == at::kFloat && t->dim() == 3 && t->is_contiguous(),
+                "tta_merge: expected contiguous float32 [B, 4+nc, A] tensors");
+  }
+  TORCH_CHECK(y.device() == cat.device() && y.size(0) == cat.size(0) && y.size(1) == cat.size(1),
+              "tta_merge: y ", y.sizes(), " and cat ", cat.sizes(), " do not match");
+  TORCH_CHECK(src_lo >= 0 && n >= 1 && src_lo + n <= y.size(2) && dst >= 0 && dst + n <= cat.size(2),
+              "tta_merge: ranges [", src_lo, ", +", n, ") / [", dst, ", +", n, ") leave y / cat");
+  c10::DeviceGuard guard(y.device());
+  auto st = c10::hip::getCurrentHIPStream(y.get_device());
+  check_rc(yolosod_tta_merge(y.data_ptr<float>(), y.size(0), y.size(1) - 4, y.size(2), (int)src_lo, (int)n,
+                             cat.data_ptr<float>(), cat.size(2), (int)dst, (float)scale, (int)flip, (float)img_w,
+                             (float)img_h, sp(st)),
+           "tta_merge");
+}
+
 // ---- shape-only (Meta) kernels ----
 Tensor mafn_meta(const Tensor& x) { return at::empty_like(x); }
 
@@ -479,6 +528,9 @@ TORCH_LIBRARY(yolosod, m) {
   m.def("nms_batched(Tensor(a!) pred, float conf_thres, float iou_thres, Tensor? classes, bool agnostic, "
         "bool multi_label, int max_det, int max_nms, float max_wh, bool in_place=True) -> (Tensor, Tensor, Tensor)");
   m.def("stem_fwd(Tensor x, Tensor weight, Tensor bias) -> (Tensor, Tensor)");
+  m.def("tta_views(Tensor x, Tensor desc, Tensor(a!)[] outs, int[] geom) -> ()");
+  m.def("tta_merge(Tensor y, Tensor(a!) cat, int src_lo, int n, int dst, float scale, int flip, int img_h, "
+        "int img_w) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(yolosod, CUDA, m) {
@@ -495,6 +547,8 @@ TORCH_LIBRARY_IMPL(yolosod, CUDA, m) {
   m.impl("detect_decode_fwd", detect_decode_fwd);
   m.impl("nms_batched", nms_batched);
   m.impl("stem_fwd", stem_fwd);
+  m.impl("tta_views", tta_views);
+  m.impl("tta_merge", tta_merge);
 }
 
 TORCH_LIBRARY_IMPL(yolosod, Meta, m) {

@@ -83,10 +83,14 @@ def frames_to_device(frames, device, who="DetectionPredictor"):
 
 class DetectionPredictor:
     def __init__(self, model, conf=0.25, iou=0.7, max_det=300, classes=None, agnostic_nms=False,
-                 multi_label=False, imgsz=640, rect=None):
+                 multi_label=False, imgsz=640, rect=None, augment=False):
         self.model = model
         self.conf, self.iou, self.max_det = conf, iou, max_det
         self.classes, self.agnostic, self.multi_label = classes, agnostic_nms, multi_label
+        # test-time augmentation (DetectionModel._predict_augment: three views, one concatenated prediction tensor in
+        # canvas pixels, so NMS and everything after it are the same; ``index`` then counts along that concatenation:
+        # model.tta_plan(canvas).locate(index) gives the branch and its anchor)
+        self.augment = bool(augment)
         p = next(model.parameters())
         self.device, self.dtype = p.device, p.dtype
         # list input (raw frames): the canvas, and whether same-shape batches take the minimal rectangle
@@ -128,10 +132,15 @@ class DetectionPredictor:
         geom = torch.tensor(rows, dtype=torch.float64).to(torch.float32).pin_memory().to(self.device, non_blocking=True)
         return Ingested(x, shapes, geom)
 
+    def _forward(self, x):
+        """The model's prediction tensor [B, 4+nc, A] for the input tensor x (A = the plan's A_tot with ``augment``)."""
+        preds = self.model(x, augment=True) if self.augment else self.model(x)
+        return preds[0] if isinstance(preds, (list, tuple)) else preds
+
     def _predict_ingested(self, ing: Ingested):
         """The model, NMS and the boxes back in each frame's pixels (predict.py:23-41: scale_boxes(img.shape[2:], boxes,
         orig_img.shape) per image) as one more launch on the padded rows."""
-        preds = self.model(ing.x)
+        preds = self._forward(ing.x)
         y = preds[0] if isinstance(preds, (list, tuple)) else preds
         out, counts, index = ops.non_max_suppression_padded(
             y, self.conf, self.iou, classes=self.classes, agnostic=self.agnostic, multi_label=self.multi_label,
@@ -146,8 +155,7 @@ class DetectionPredictor:
         if isinstance(im, (list, tuple)):
             return self._predict_ingested(self.ingest(im))
         x = self.preprocess(im)
-        preds = self.model(x)
-        y = preds[0] if isinstance(preds, (list, tuple)) else preds
+        y = self._forward(x)
         # in_place=False: the reference's postprocess rewrites preds[:, :4] to xyxy (ops.py:167, in_place=True) and
         # then drops preds; y is local here too, so the rewrite (17 MB at bs 32) is skipped - same detections
         out, counts, index = ops.non_max_suppression_padded(
@@ -201,6 +209,8 @@ class SlicedPredictor:
     the frame's memory, ``batch`` tiles per model call, tiles of different frames share a call) -> :meth:`merge`
     (``_hip.tile_merge`` per call into merged [F, 4+nc, S*A], frame pixels) -> :meth:`postprocess` (NMS on merged,
     clip to the frame). ``index`` of a detection is ``slot * A + anchor``; ``plan.slot(frame, slot)`` is its tile.
+
+    Test-time augmentation (``DetectionPredictor(augment=True)``) is out of scope here: the tiles are run at one scale.
 
     ``cut_margin`` (tile pixels; None: off): a candidate whose box comes within it of a tile edge that is interior to
     the frame is dropped before NMS - the tile saw the object truncated, a neighbouring tile or the whole-frame slot

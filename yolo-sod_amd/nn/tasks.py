@@ -199,7 +199,13 @@ class BaseModel(nn.Module):
         return self.predict(x, *args, **kwargs)
 
     def predict(self, x, profile=False, visualize=False, augment=False, embed=None):
+        if augment:
+            return self._predict_augment(x)
         return self._predict_once(x)
+
+    def _predict_augment(self, x):
+        """tasks.py:158-163: only a DetectionModel has augmented inference."""
+        raise NotImplementedError(f"{type(self).__name__} does not support augment=True")
 
     def _predict_once(self, x):
         """tasks.py:165-192: run layers in YAML order, keeping the outputs other layers read."""
@@ -510,6 +516,44 @@ class DetectionModel(BaseModel):
         initialize_weights(self)
         if probe_stats:
             self._load_probe_stats()
+
+    def tta_plan(self, shape, scales=None, flips=None):
+        """The :class:`~yolosod_amd.data.tta.TTAPlan` of a batch of this (h, w), kept per shape (it caches the
+        descriptor tables it uploads)."""
+        from ..data.tta import DEFAULT_FLIPS, DEFAULT_SCALES, TTAPlan
+        scales = DEFAULT_SCALES if scales is None else tuple(scales)
+        flips = DEFAULT_FLIPS if flips is None else tuple(flips)
+        plans = self.__dict__.setdefault("_tta_plans", {})
+        key = (int(shape[0]), int(shape[1]), scales, flips)
+        plan = plans.get(key)
+        if plan is None:
+            if len(plans) >= 16:
+                plans.clear()
+            strides = [int(s) for s in self.stride.tolist()]
+            plan = plans[key] = TTAPlan(key[:2], scales, flips, stride=strides, nl=self.model[-1].nl)
+        return plan
+
+    def _predict_augment(self, x, scales=None, flips=None):
+        """tasks.py:381-418: the model on three views of the batch (scales 1 / 0.83 / 0.67, the second flipped
+        left-right), each branch's boxes de-scaled and de-flipped, the tails of the first and last branch clipped and
+        everything concatenated along the anchor axis for one NMS. Returns ``(cat [B, 4+nc, A_tot], None)`` in the
+        batch's own pixels. The views are one HIP launch (``_hip.tta_views``) and each branch goes into ``cat`` with
+        one more (``_hip.tta_merge``): no torch op touches the tensors, and nothing syncs the host. ``scales`` /
+        ``flips``: other views than the reference's (``data.tta.TTAPlan``)."""
+        if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+            raise RuntimeError("predict(augment=True): HIP kernel requires GPU tensors (got device "
+                               f"{getattr(x, 'device', type(x).__name__)}); no CPU fallback")
+        if x.dim() != 4:
+            raise RuntimeError(f"predict(augment=True): expected [B, C, H, W], got shape {tuple(x.shape)}")
+        plan = self.tta_plan(x.shape[-2:], scales, flips)
+        cat = None
+        for k, xi in enumerate(plan.make_views(x)):
+            yi = self._predict_once(xi)
+            yi = yi[0] if isinstance(yi, (list, tuple)) else yi
+            if cat is None:
+                cat = torch.empty((yi.shape[0], yi.shape[1], plan.A_tot), dtype=torch.float32, device=yi.device)
+            plan.merge(k, yi, cat)
+        return cat, None
 
     def _probe_strides(self, ch: int, s: int = 256) -> torch.Tensor:
         """Shape-only replica of the reference's 256x256 stride probe (tasks.py:369), on the meta device."""
