@@ -289,6 +289,16 @@ int yolosod_conv3x3_silu_ex(const float* x, float* y, long y_bstride, const floa
 int yolosod_conv3x3_silu_xs(const float* x, long x_bstride, float* y, long y_bstride, const float* res, long res_bstride,
                             int B, int cin, int cout, int H, int W, const float* bias, const void* prep,
                             size_t prep_bytes, void* stream);
+/* A C2f Bottleneck of 32 channels (Cin = Cmid = Cout = 32: the two P2 C2fs) as one launch:
+ * y = [res +] SiLU(conv3x3(SiLU(conv3x3(x, W1) + bias1), W2) + bias2), the intermediate map kept on chip, bit-identical
+ * to two yolosod_conv3x3_silu_xs launches. W % 4 == 0 and 16-byte aligned images only (others: error); image b of
+ * x / y / res at x + b*x_bstride / y + b*y_bstride / res + b*res_bstride (channel slices of a concat buffer); res NULL:
+ * no shortcut; prep1 / prep2: yolosod_conv3x3_prepare_ex(w, 32, 32, ...) of the two convs. y must not alias x / res.
+ * The entry always runs the one launch; yolosod_debug_bottleneck3x3_fused says when it is the faster choice. */
+int yolosod_bottleneck3x3_silu_xs(const float* x, long x_bstride, float* y, long y_bstride, const float* res,
+                                  long res_bstride, int B, int H, int W, const float* bias1, const void* prep1,
+                                  size_t prep1_bytes, const float* bias2, const void* prep2, size_t prep2_bytes,
+                                  void* stream);
 
 /* Thin fused 1x1 convolution of the backbone (conv.py:37-55 after fuse(), 1x1 case): out = SiLU(W x + bias) (+ res)
  * for Cout in {64, 128}, Cin in {64, 96, 128, 192, 256}, HW % 64 == 0; x / out / res may be channel slices (batch
@@ -446,6 +456,13 @@ int yolosod_debug_conv3x3_form(int B, int cout, int H, int W);
 /* As yolosod_debug_conv3x3_form for a known Cin: groups 3 / 4 are chosen (automatically, or forced) for Cin 32 ->
  * Cout 32 only, and yolosod_debug_conv3x3_form answers for every other Cin. */
 int yolosod_debug_conv3x3_form_ex(int B, int cin, int cout, int H, int W);
+/* Whether a [B][32][H][W] Bottleneck is to run as yolosod_bottleneck3x3_silu_xs (1) or as the two conv launches (0)
+ * under the current setting: automatically, from a map size (B*32*H*W*4 bytes) at which the pair's intermediate no
+ * longer stays in cache between its launches; never for W % 4 != 0. Host-side, no GPU needed. */
+int yolosod_debug_bottleneck3x3_fused(int B, int H, int W);
+/* Test / measurement hook for the answer above: -1 automatic (default), 0 never, 1 every shape the kernel takes.
+ * Other values are ignored. Returns the previous value. */
+int yolosod_debug_set_bottleneck3x3_fuse(int mode);
 void yolosod_debug_set_gemm_x2(int on);
 /* Test hook: the bf16 decomposed SwinBlock's depthwise conv + token layout and LN1 in one pass
  * (swin_tokens_ln_bf16_kernel, 1, default) or as two kernels (0);

@@ -1,7 +1,7 @@
 """Micro-benchmark: the stride-1 3x3 convs of the n640 step (bs 32) - the Detect towers and the backbone's / neck's C2f
 Bottleneck convs (Cout 32 .. 256, with and without the shortcut) - on the fp16-split kernel vs MIOpen (F.conv2d without
 bias + the HIP bias / SiLU (+ shortcut) epilogue, as the executor runs it). GPU only.
-python scripts/bench_conv3x3.py [forms | <abl>,...]; YOLOSOD_LIB_AB=<lib> times another build of the library."""
+python scripts/bench_conv3x3.py [forms | bottleneck [H [batches]] | <abl>,...]; YOLOSOD_LIB_AB=<lib> times another build of the library."""
 import sys
 from pathlib import Path
 
@@ -31,7 +31,7 @@ def timed(fn, reps=50):
     return e0.elapsed_time(e1) / reps
 
 
-ABL = [int(a) for a in sys.argv[1].split(",")] if len(sys.argv) > 1 and sys.argv[1] != "forms" else []
+ABL = [int(a) for a in sys.argv[1].split(",")] if len(sys.argv) > 1 and sys.argv[1] not in ("forms", "bottleneck") else []
 if ABL:  # timing ablations of the kernel (wrong results): see yolosod_debug_set_conv3x3_abl
     lib = _hip.load_library()
     for shape in SHAPES[:2]:
@@ -50,6 +50,37 @@ if ABL:  # timing ablations of the kernel (wrong results): see yolosod_debug_set
             print(f"{str(shape):22s} abl {a:2d} {t_k:7.3f} ms ({gf / t_k:6.1f} TF/s)  max|y - y_abl0| {d:.3g}",
                   flush=True)
         lib.yolosod_debug_set_conv3x3_abl(0)
+    sys.exit(0)
+
+if len(sys.argv) > 1 and sys.argv[1] == "bottleneck":
+    # the 32-channel Bottleneck (32 -> 32 -> 32 with the shortcut) in place in a C2f's 96-channel buffer, input
+    # z[:, 32:64] and output z[:, 64:96]: the fused launch against the two conv launches (each timed alone, their sum,
+    # and the two back to back); python scripts/bench_conv3x3.py bottleneck [H [batches]], every batch twice,
+    # alternating the two sides
+    H = int(sys.argv[2]) if len(sys.argv) > 2 else 160
+    batches = [int(a) for a in sys.argv[3].split(",")] if len(sys.argv) > 3 else [2, 4, 8, 16, 32]
+    for B in batches * 2:
+        z = torch.randn(B, 96, H, H, device=dev)
+        t = torch.empty(B, 32, H, H, device=dev)
+        x, y = z[:, 32:64], z[:, 64:96]
+        w1, w2 = (torch.randn(32, 32, 3, 3, device=dev) * 0.05 for _ in range(2))
+        b1, b2 = (torch.randn(32, device=dev) * 0.1 for _ in range(2))
+        p1, p2 = _hip.conv3x3_prepare(w1), _hip.conv3x3_prepare(w2)
+        cv1 = lambda: _hip.conv3x3_silu(x, b1, lambda: p1, 32, out=t)  # noqa: E731
+        cv2 = lambda: _hip.conv3x3_silu(t, b2, lambda: p2, 32, out=y, res=x)  # noqa: E731
+        fused = lambda: _hip.bottleneck3x3_silu(x, b1, lambda: p1, b2, lambda: p2, out=y, res=x)  # noqa: E731
+        cv1(), cv2()
+        y0 = y.clone()
+        fused()
+        same = torch.equal(y, y0)
+        row = []
+        for _ in range(2):
+            t1, t2 = timed(cv1), timed(cv2)
+            row.append((timed(fused), t1, t2, timed(lambda: (cv1(), cv2()))))
+        mb = B * 32 * H * H * 4 / 1e6
+        print(f"B {B:2d} x 32 x {H}^2 ({mb:6.1f} MB/map) equal {same}  " + "   ".join(
+            f"fused {f:.4f}  cv1 {a:.4f} + cv2 {b:.4f} = {a + b:.4f}  pair back-to-back {p:.4f} ms"
+            for f, a, b, p in row), flush=True)
     sys.exit(0)
 
 # every stride-1 3x3 launch shape of the n640 step at bs 32: (input shape, Cout, residual). Detect towers (Cout 64),

@@ -1,6 +1,8 @@
 """A few launches of one stride-1 3x3 conv at 32 x Cin x 160 x 160 on the fp16-split kernel, for rocprofv3 --pmc passes:
 python scripts/c3_pmc.py [cin cout [form]]   (default 64 64: the P2 Detect tower conv; 32 32: layer 3 / layer 27;
-form: yolosod_debug_set_conv3x3_form, 0 = the automatic choice). GPU only."""
+form: yolosod_debug_set_conv3x3_form, 0 = the automatic choice), or
+python scripts/c3_pmc.py bottleneck fused|pair [B]   the 32-channel Bottleneck with the shortcut in place in a
+96-channel buffer, as one launch or as its two conv launches. GPU only."""
 import sys
 from pathlib import Path
 
@@ -12,6 +14,23 @@ import yolosod_import  # noqa: E402,F401
 from yolosod_amd import _hip  # noqa: E402
 
 dev = torch.device("cuda", 0)
+if len(sys.argv) > 2 and sys.argv[1] == "bottleneck":
+    B, H, W = int(sys.argv[3]) if len(sys.argv) > 3 else 32, 160, 160
+    z = torch.randn(B, 96, H, W, device=dev)
+    t = torch.empty(B, 32, H, W, device=dev)
+    x, y = z[:, 32:64], z[:, 64:96]
+    w1, w2 = (torch.randn(32, 32, 3, 3, device=dev) * 0.05 for _ in range(2))
+    b1, b2 = (torch.randn(32, device=dev) * 0.1 for _ in range(2))
+    p1, p2 = _hip.conv3x3_prepare(w1), _hip.conv3x3_prepare(w2)
+    for _ in range(5):
+        if sys.argv[2] == "fused":
+            _hip.bottleneck3x3_silu(x, b1, lambda: p1, b2, lambda: p2, out=y, res=x)
+        else:
+            _hip.conv3x3_silu(x, b1, lambda: p1, 32, out=t)
+            _hip.conv3x3_silu(t, b2, lambda: p2, 32, out=y, res=x)
+    torch.cuda.synchronize()
+    print("ok")
+    sys.exit(0)
 cin, cout = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (64, 64)
 form = int(sys.argv[3]) if len(sys.argv) > 3 else 0
 B, H, W = 32, 160, 160

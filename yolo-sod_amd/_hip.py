@@ -110,6 +110,9 @@ SIGNATURES = {
     "yolosod_debug_set_conv3x3_form": (_i, [_i]),
     "yolosod_debug_conv3x3_form": (_i, [_i, _i, _i, _i]),
     "yolosod_debug_conv3x3_form_ex": (_i, [_i, _i, _i, _i, _i]),
+    "yolosod_bottleneck3x3_silu_xs": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "yolosod_debug_bottleneck3x3_fused": (_i, [_i, _i, _i]),
+    "yolosod_debug_set_bottleneck3x3_fuse": (_i, [_i]),
     "yolosod_debug_set_conv1x1x2_form": (_i, [_i]),
     "yolosod_debug_conv1x1x2_form": (_i, [_i, _i, _i, _i]),
     "yolosod_debug_set_conv3x3s2_abl": (_i, [_i]),
@@ -910,6 +913,43 @@ def conv3x3_silu(x, bias, prep, cout=64, out=None, res=None, op="conv3x3"):
                                            blk.data_ptr(), blk.numel(), _stream(x.device))
 
     _check(_launch((op, tuple(x.shape), cout if res is None else (cout, "res")), x.device, run), "conv3x3")
+    return y
+
+
+def bottleneck3x3_fused(B, H, W) -> bool:
+    """Whether a [B, 32, H, W] Bottleneck is to run as one launch (yolosod_debug_bottleneck3x3_fused: large maps, or
+    the form forced by yolosod_debug_set_bottleneck3x3_fuse)."""
+    return bool(load_library().yolosod_debug_bottleneck3x3_fused(int(B), int(H), int(W)))
+
+
+def bottleneck3x3_silu(x, bias1, prep1, bias2, prep2, out=None, res=None, op="bottleneck3x3"):
+    """[res +] SiLU(conv3x3(SiLU(conv3x3(x) + bias1)) + bias2) for 32 -> 32 -> 32 channels as one launch
+    (csrc/conv3x3.hip, bottleneck3x3_c32_kernel), bit-identical to conv3x3_silu twice; ``prep1`` / ``prep2``: callables
+    returning the cached prepared blocks of the two weights; ``out`` / ``res`` / ``op`` as conv3x3_silu."""
+    lib = load_library()
+    B, C, H, W = x.shape
+    if C != 32:
+        raise RuntimeError(f"bottleneck3x3: {C} channels (32 only)")
+    if out is None:
+        y = torch.empty((B, 32, H, W), dtype=torch.float32, device=x.device)
+    else:
+        _img_view(out, (B, 32, H, W), "bottleneck3x3: out")
+        y = out
+    if res is not None:
+        _img_view(res, (B, 32, H, W), "bottleneck3x3: res")
+    b1 = bias1.detach().float().contiguous()
+    b2 = bias2.detach().float().contiguous()
+
+    def run():
+        blk1, blk2 = prep1(), prep2()
+        _img_view(x, (B, 32, H, W), "bottleneck3x3: x")
+        return lib.yolosod_bottleneck3x3_silu_xs(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0),
+                                                 None if res is None else res.data_ptr(),
+                                                 0 if res is None else res.stride(0), B, H, W, _dev(b1, "bias1"),
+                                                 blk1.data_ptr(), blk1.numel(), _dev(b2, "bias2"), blk2.data_ptr(),
+                                                 blk2.numel(), _stream(x.device))
+
+    _check(_launch((op, tuple(x.shape), 32 if res is None else (32, "res")), x.device, run), "bottleneck3x3")
     return y
 
 

@@ -597,6 +597,299 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c32_kernel(Args p) {
   conv3x3_p_body<G, 1, RES, F>(p);
 }
 
+// ---- The P2 C2f Bottleneck as one launch ----------------------------------------------------------------------------
+// y = [res +] SiLU(conv3x3(SiLU(conv3x3(x, W1) + b1), W2) + b2), Cin = Cmid = Cout = 32, stride 1, pad 1, fp32 in and
+// out, W % 4 == 0: the two launches of conv3x3_p_kernel<0, 1, *> with the intermediate map kept in LDS instead of
+// written to memory and read back (at 160^2 and the bench's batch the pair moves five 105 MB maps, this launch two).
+// Bit-identical to the pair: per output element of either conv the additions run tap 0 .. 8, then xh.w1, xl.w0, xh.w0
+// on v_mfma_f32_16x16x32_f16, with the same channel-to-k mapping; the epilogue is the pair's expression; the
+// intermediate is rounded to fp32, zeroed outside the image (it is the second conv's zero padding, not SiLU(b1)), and
+// split with the split4x of the second launch's staging; the shortcut is the exact fp32 input, added separately.
+//
+// One 512-thread workgroup per CU (157,696 B of LDS), persistent over the 32 x 8 output tiles of its XCD as above:
+//   stage   the tile's 12 rows x 40 columns of input (columns 32 tx - 4 .. + 35: ten whole groups of four pixels per
+//           row, the 36-wide halo of both convs plus two unused columns each side, so every staged item is a whole
+//           group) from registers into two fp16 planes [row][40][PS]; the registers were loaded during the previous
+//           tile's first conv;
+//   conv 1  on the 10 x 34 intermediate halo taken as 340 consecutive pixels in 22 blocks of 16 (24 slots: 6 per wave
+//           quarter, wave w = channel block w & 1 x quarter w >> 1; 24 slots against the 16 of the first launch, so
+//           the MFMA work of the pair is x 1.25). The weights are the MFMA's A operand here, so a lane holds four
+//           consecutive channels of one pixel and the split intermediate goes to its planes [pixel][PS] with 8-byte
+//           stores;
+//   conv 2  as conv3x3_p_body (pixels the A operand, four 16 x 1 blocks per wave) from the intermediate planes; the
+//           shortcut's loads are issued before its taps, the 16-byte non-temporal stores are the pair's.
+// Two barriers per tile: staged input visible / intermediate visible. Weight fragments from L2 through a register ring
+// that runs across taps, convs and tiles, five taps ahead (bn_taps). Measured and dropped: fragments one tap
+// ahead as in conv3x3_p_body (8 % slower), both channel blocks on every wave (half the LDS reads, twice the weight
+// loads: 10 % slower), the second conv's weights resident in registers (no faster).
+constexpr int BN_NT = 512;
+constexpr int BN_IW = 40, BN_IH = TH + 4;                        // staged input region
+constexpr int BN_MW = TW + 2, BN_NM = (TH + 2) * BN_MW;          // intermediate: 34 wide, 340 pixels
+constexpr int BN_PL1 = BN_IH * BN_IW * PS, BN_PL2 = BN_NM * PS;  // planes (halves)
+constexpr int BN_NQ = 8 * BN_IH * (BN_IW / 4);                   // 960 staged items (quad, row, group of four pixels)
+constexpr int BN_NIT = (BN_NQ + BN_NT - 1) / BN_NT;              // 2
+constexpr int BN_S1 = 6, BN_S2 = 4;                              // block slots per wave: conv 1 / conv 2
+constexpr int BN_LDS = (2 * BN_PL1 + 2 * BN_PL2) * 2 + 64 * 4;
+static_assert(4 * BN_S1 * 16 >= BN_NM && BN_LDS <= 160 * 1024, "bottleneck3x3 geometry");
+
+struct BnArgs {
+  const float* x;
+  long xbs;
+  float* y;
+  long ybs;
+  const float* res;  // RES: the shortcut (the Bottleneck's own input), image b at res + b rbs
+  long rbs;
+  const h16_t *wp1, *wp2;  // prepared planes of the two convs (yolosod_conv3x3_prepare_ex, 32 -> 32)
+  const float *b1, *b2;
+  int H, W, tiles_x, tiles_y, ntiles;
+  unsigned* range_flag;
+  const unsigned *prep_flag1, *prep_flag2;
+};
+
+// The nine taps of one conv over NS pixel blocks of this wave (base pixels bpx in planes P, P + PLN of row stride RS):
+// pixel fragments one block ahead of their MFMAs (conv3x3_p_body's schedule); per_tap(t) is issued at the head of tap
+// t. Weight fragments come from a ring of BN_WD register slots that runs through both convs of every tile (18 tap
+// steps per tile, step S0 + t here; the weights do not depend on the tile): step s uses slot s % BN_WD, and the head
+// of step s issues wld(step s + BN_WD - 1) into the slot step s - 1 has just finished with, so a fragment is five taps
+// in flight and no tap, phase or tile starts on an exposed L2 round trip. WA: the weights as the A operand.
+constexpr int BN_WD = 6;
+static_assert(18 % BN_WD == 0, "bottleneck3x3: the weight ring's slots are static per tap step");
+template <int NS, int RS, int PLN, bool WA, int S0, class WLoad, class PerTap>
+__device__ __forceinline__ void bn_taps(const h16_t* P, const int (&bpx)[NS], int g, f16x8_t (&wr)[BN_WD][2],
+                                        f32x4 (&acc)[NS], WLoad&& wld, PerTap&& per_tap) {
+  auto rd = [&](int t, int cb, f16x8_t& h, f16x8_t& l) __attribute__((always_inline)) {
+    const h16_t* src = P + (bpx[cb] + (t / 3) * RS + (t % 3)) * PS + 8 * g;
+    h = *reinterpret_cast<const f16x8_t*>(src);
+    l = *reinterpret_cast<const f16x8_t*>(src + PLN);
+  };
+  f16x8_t nh, nl;
+  rd(0, 0, nh, nl);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+  for (int t = 0; t < 9; ++t) {
+    const int sn = (S0 + t + BN_WD - 1) % 18;
+    wld(sn, wr[sn % BN_WD]);
+    per_tap(t);
+    __builtin_amdgcn_sched_barrier(0);
+    const f16x8_t w0 = wr[(S0 + t) % BN_WD][0], w1 = wr[(S0 + t) % BN_WD][1];
+#pragma unroll
+    for (int cb = 0; cb < NS; ++cb) {
+      const f16x8_t xh = nh, xlo = nl;
+      if (cb < NS - 1) rd(t, cb + 1, nh, nl);
+      else if (t < 8) rd(t + 1, 0, nh, nl);
+      f32x4 c;
+      if constexpr (WA) {  // the same three products, small terms first, with the operand roles exchanged
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(w1, xh, acc[cb], 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0, xlo, c, 0, 0, 0);
+        acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w0, xh, c, 0, 0, 0);
+      } else {
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, w1, acc[cb], 0, 0, 0);
+        c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xlo, w0, c, 0, 0, 0);
+        acc[cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, w0, c, 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int cb = 0; cb < NS; ++cb) {
+      if (cb < NS - 1 || t < 8) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);  // DS read
+      __builtin_amdgcn_sched_group_barrier(0x008, 3, 0);                            // MFMA
+    }
+  }
+}
+
+template <bool RES>
+__global__ __launch_bounds__(BN_NT) void bottleneck3x3_c32_kernel(BnArgs p) {
+  __shared__ __attribute__((aligned(16))) h16_t Pi[2 * BN_PL1];  // staged input, hi / lo
+  __shared__ __attribute__((aligned(16))) h16_t Pm[2 * BN_PL2];  // intermediate, hi / lo
+  __shared__ __attribute__((aligned(16))) float bsh[64];         // b1, b2
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int l15 = lane & 15, g = lane >> 4;
+  const int rp = wid & 1, qt = wid >> 1;  // channel block, quarter of the block slots
+  const int H = p.H, W = p.W, HWi = H * W;
+  float rng = 0.f;
+  if (tid < 64) bsh[tid] = tid < 32 ? p.b1[tid] : p.b2[tid - 32];  // ordered before use by the loop's barriers
+
+  const int nj = gridDim.x >> 3, j = blockIdx.x >> 3, xcd = blockIdx.x & 7;
+  const int per = (p.ntiles + 7) >> 3;
+  const int t_beg = xcd * per + j, t_end = min((xcd + 1) * per, p.ntiles);
+  if (t_beg >= t_end) return;
+  const int n_it = (t_end - t_beg + nj - 1) / nj;
+
+  auto rsrc = [&](const void* base, unsigned bytes) {
+    const unsigned long long a = (unsigned long long)base;
+    return __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(a >> 32)) << 32) |
+                (unsigned)__builtin_amdgcn_readfirstlane((unsigned)a)),
+        (short)0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+  };
+  const __amdgpu_buffer_rsrc_t rw1 = rsrc(p.wp1, 9u * 4 * 1024), rw2 = rsrc(p.wp2, 9u * 4 * 1024);
+  // staging item e: sixteen consecutive lanes take the 8 quads of two pixel groups (conv3x3_p_body's bank layout)
+  int pk[BN_NIT], el0[BN_NIT];
+#pragma unroll
+  for (int i = 0; i < BN_NIT; ++i) {
+    const int e = min(tid + BN_NT * i, BN_NQ - 1);
+    const int f = (e >> 4) * 2 + (e & 1), quad = (e >> 1) & 7;
+    const int hy = f / (BN_IW / 4), gx = 4 * (f % (BN_IW / 4));
+    pk[i] = (quad << 16) | (hy << 8) | gx;
+    el0[i] = 4 * quad * HWi + hy * W + gx;
+  }
+  struct It {
+    int b, ty, tx;
+  };
+  auto it_of = [&](int it) __attribute__((always_inline)) {
+    const int t = t_beg + it * nj;
+    It r;
+    r.tx = t % p.tiles_x;
+    r.ty = (t / p.tiles_x) % p.tiles_y;
+    r.b = t / (p.tiles_x * p.tiles_y);
+    return r;
+  };
+  f32x4 sv[BN_NIT][4];  // sv[i][c]: the group's four pixels of channel c of the item's quad
+  unsigned okb_ld = 0;
+  auto load_part = [&](const It& r, int k0, int k1) __attribute__((always_inline)) {
+    const int iy0 = TH * r.ty - 2, ix0 = TW * r.tx - 4;
+    const __amdgpu_buffer_rsrc_t ri = rsrc(p.x + (long)r.b * p.xbs, (unsigned)(32 * HWi * 4));
+    const int toff = iy0 * W + ix0;
+    if (k0 == 0) {  // W % 4 == 0: a group lies wholly inside or outside the image
+      unsigned okb = 0;
+#pragma unroll
+      for (int i = 0; i < BN_NIT; ++i) {
+        const int hy = (pk[i] >> 8) & 255, gx = pk[i] & 255;
+        okb |= ((unsigned)(iy0 + hy) < (unsigned)H && (unsigned)(ix0 + gx) < (unsigned)W) ? (1u << i) : 0u;
+      }
+      okb_ld = okb;
+    }
+#pragma unroll
+    for (int i = 0; i < BN_NIT; ++i) {
+      const unsigned vo = ((okb_ld >> i) & 1u) ? (unsigned)((el0[i] + toff) * 4) : 0xfffffff0u;  // masked: no access
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+        if (4 * i + c >= k0 && 4 * i + c < k1)
+          sv[i][c] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(ri, vo + c * HWi * 4, 0, 0));
+    }
+  };
+  // four channels of one pixel: split, range, the two planes
+  auto put = [&](h16_t* P, int pln, int px, int ch, f32x4 v) __attribute__((always_inline)) {
+    uint2 hh, ll;
+    split4x(v, hh, ll);
+    rng = range_acc(rng, v);
+    h16_t* d = P + px * PS + ch;
+    *reinterpret_cast<uint2*>(d) = hh;
+    *reinterpret_cast<uint2*>(d + pln) = ll;
+  };
+  // conv 1: slot s of this wave is block 6 qt + s of the 340 intermediate pixels, lane pixel m = 16 block + l15 (past
+  // the last pixel: pixel 339 again, unstored) at (m / 34, m % 34); its taps start at staged (row, column + 2)
+  int bpx1[BN_S1], bpx2[BN_S2];
+#pragma unroll
+  for (int s = 0; s < BN_S1; ++s) {
+    const int m = min(16 * (BN_S1 * qt + s) + l15, BN_NM - 1);
+    bpx1[s] = (m / BN_MW) * BN_IW + m % BN_MW + 2;
+  }
+  // conv 2: block bi = 4 qt + cb is row bi >> 1, columns 16 (bi & 1) .. + 15 of the tile
+#pragma unroll
+  for (int cb = 0; cb < BN_S2; ++cb) {
+    const int bi = BN_S2 * qt + cb;
+    bpx2[cb] = (bi >> 1) * BN_MW + (bi & 1) * 16 + l15;
+  }
+  f32x4 acc1[BN_S1], acc2[BN_S2];
+  const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int s = 0; s < BN_S1; ++s) acc1[s] = z4;
+#pragma unroll
+  for (int cb = 0; cb < BN_S2; ++cb) acc2[cb] = z4;
+
+  // the weight ring (bn_taps): tap step s of a tile is conv s / 9, tap s % 9; this wave's channel block rp, both planes
+  // ([tap][channel block][plane][lane][16 bytes] in a prepared block)
+  f16x8_t wr[BN_WD][2];
+  auto wld = [&](int step, f16x8_t (&w)[2]) __attribute__((always_inline)) {
+    const int st = __builtin_amdgcn_readfirstlane((step % 9) * 4 * 1024);
+#pragma unroll
+    for (int pl = 0; pl < 2; ++pl)
+      w[pl] = __builtin_bit_cast(f16x8_t, __builtin_amdgcn_raw_buffer_load_b128(
+                                              step < 9 ? rw1 : rw2, (unsigned)(((rp * 2 + pl) * 64 + lane) * 16), st, 0));
+  };
+#pragma unroll
+  for (int s = 0; s < BN_WD - 1; ++s) wld(s, wr[s]);
+
+  It cur = it_of(0);
+  load_part(cur, 0, 4 * BN_NIT);
+  for (int it = 0; it < n_it; ++it) {
+    const It r = cur;
+    const unsigned okb = okb_ld;
+    // every wave is past the previous tile's second barrier, that is done with its reads of the input planes
+#pragma unroll
+    for (int i = 0; i < BN_NIT; ++i) {
+      if (tid + BN_NT * i < BN_NQ) {
+        const int quad = pk[i] >> 16, px = ((pk[i] >> 8) & 255) * BN_IW + (pk[i] & 255);
+        const bool ok = (okb >> i) & 1u;
+#pragma unroll
+        for (int jx = 0; jx < 4; ++jx)
+          put(Pi, BN_PL1, px + jx, 4 * quad, ok ? f32x4{sv[i][0][jx], sv[i][1][jx], sv[i][2][jx], sv[i][3][jx]} : z4);
+      }
+    }
+    __syncthreads();  // the staged input is visible; every wave is done with the previous tile's intermediate
+    if (it + 1 < n_it) cur = it_of(it + 1);  // the last tile reloads itself (unconditional loads; L2-hot)
+    bn_taps<BN_S1, BN_IW, BN_PL1, true, 0>(Pi, bpx1, g, wr, acc1, wld, [&](int t) __attribute__((always_inline)) {
+      load_part(cur, t, t + 1);  // the next tile's eight loads, one per tap
+    });
+    // the intermediate: SiLU(conv + b1) rounded to fp32 as the first launch stored it, zero outside the image, split
+    // as the second launch's staging splits what it loads (the empty statement hides the producing multiply from the
+    // split's subtraction)
+    auto mid = [&](float a, float b, int m) __attribute__((always_inline)) {
+      float v = silu_fast_(a * (1.0f / WSC) + b);
+      asm volatile("" : "+v"(v));
+      const int my = m / BN_MW, mx = m - my * BN_MW;
+      const bool in = (unsigned)(TH * r.ty - 1 + my) < (unsigned)H && (unsigned)(TW * r.tx - 1 + mx) < (unsigned)W;
+      return in ? v : 0.f;
+    };
+    // lane: channels 16 rp + 4 g .. + 3 of pixel m (the weights were the A operand)
+    const f32x4 b1v = *reinterpret_cast<const f32x4*>(bsh + 16 * rp + 4 * g);
+#pragma unroll
+    for (int s = 0; s < BN_S1; ++s) {
+      const int m = 16 * (BN_S1 * qt + s) + l15;
+      const f32x4 v = f32x4{mid(acc1[s][0], b1v[0], m), mid(acc1[s][1], b1v[1], m), mid(acc1[s][2], b1v[2], m),
+                            mid(acc1[s][3], b1v[3], m)};
+      if (m < BN_NM) put(Pm, BN_PL2, m, 16 * rp + 4 * g, v);
+      acc1[s] = z4;
+    }
+    __syncthreads();  // the intermediate is visible; every wave is done with the input planes
+    // the shortcut's loads ahead of the second conv's taps (a masked block goes out of the buffer range)
+    const int cho = (16 * rp + l15) * HWi;
+    f32x4 rv[BN_S2];
+    if constexpr (RES) {
+      const __amdgpu_buffer_rsrc_t rr = rsrc(p.res + (long)r.b * p.rbs, (unsigned)(32 * HWi * 4));
+#pragma unroll
+      for (int cb = 0; cb < BN_S2; ++cb) {
+        const int bi = BN_S2 * qt + cb;
+        const int oy = r.ty * TH + (bi >> 1), ox = r.tx * TW + (bi & 1) * 16 + 4 * g;
+        const unsigned vo = oy < H && ox < W ? (unsigned)((cho + oy * W + ox) * 4) : 0xfffffff0u;
+        rv[cb] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rr, vo, 0, 0));
+      }
+    }
+    bn_taps<BN_S2, BN_MW, BN_PL2, false, 9>(Pm, bpx2, g, wr, acc2, wld, [&](int) __attribute__((always_inline)) {});
+    float* yb = p.y + (long)r.b * p.ybs;
+    const float bv = bsh[32 + 16 * rp + l15];
+#pragma unroll
+    for (int cb = 0; cb < BN_S2; ++cb) {
+      const int bi = BN_S2 * qt + cb;
+      const int oy = r.ty * TH + (bi >> 1), ox = r.tx * TW + (bi & 1) * 16 + 4 * g;
+      const bool live = oy < H && ox < W;
+      f32x4 o;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o[e] = silu_fast_(acc2[cb][e] * (1.0f / WSC) + bv);
+      if constexpr (RES) {
+#pragma clang fp contract(off)  // a separately rounded add, as x + cv2(...): no fma with SiLU's last multiply
+        if (live) o = o + rv[cb];
+      }
+      if (live) __builtin_nontemporal_store(o, reinterpret_cast<f32x4*>(yb + cho + oy * W + ox));
+      acc2[cb] = z4;
+    }
+  }
+  range_report(p.range_flag, rng);
+  if (p.range_flag && blockIdx.x == 0 && threadIdx.x == 0 &&
+      ((p.prep_flag1 && *p.prep_flag1) || (p.prep_flag2 && *p.prep_flag2)))
+    *p.range_flag = 1u;
+}
+
 // W [64][Cin][3][3] -> fragment-major planes of 64 W (see the file comment); one thread per (output channel, input
 // channel, tap). The block's own range word records whether 64 W left fp16's range (re-reported by every launch).
 __global__ __launch_bounds__(256) void conv3x3_prep_kernel(const float* __restrict__ w, int cin, int cout,
@@ -841,6 +1134,70 @@ YS_EXPORT int yolosod_conv3x3_silu_ex(const float* x, float* y, long y_bstride, 
                                       size_t prep_bytes, void* stream) {
   return yolosod_conv3x3_silu_xs(x, (long)cin * H * W, y, y_bstride, res, res_bstride, B, cin, cout, H, W, bias, prep,
                                  prep_bytes, stream);
+}
+
+// ---- the fused Bottleneck (32 -> 32 -> 32) -------------------------------------------------------------------------
+// Routing: the pair's intermediate map costs memory traffic only when it does not stay in cache between the two
+// launches, so the fused launch is the automatic choice from BN_FUSE_MIN_BYTES of one map (B 32 H W 4) up: the
+// smallest size measured (160^2, batches 2 .. 32) from which it beat the pair at every larger one, never below 16 MB
+// (DESIGN 24). yolosod_debug_set_bottleneck3x3_fuse: -1 automatic, 0 never, 1 every shape the kernel takes.
+static const long BN_FUSE_MIN_BYTES = 8L * 32 * 160 * 160 * 4;
+static int g_bn_fuse = -1;
+YS_EXPORT int yolosod_debug_set_bottleneck3x3_fuse(int mode) {
+  const int old = g_bn_fuse;
+  if (mode >= -1 && mode <= 1) g_bn_fuse = mode;
+  return old;
+}
+
+static bool bn_shape_ok(int B, int H, int W) {
+  return B > 0 && H > 0 && W > 0 && W % 4 == 0 && 32L * H * W * 4 < (1L << 31);
+}
+
+// Whether a [B][32][H][W] Bottleneck is to run as the fused launch under the current setting (host only).
+YS_EXPORT int yolosod_debug_bottleneck3x3_fused(int B, int H, int W) {
+  if (!bn_shape_ok(B, H, W) || g_bn_fuse == 0) return 0;
+  return g_bn_fuse == 1 || (long)B * 32 * H * W * 4 >= BN_FUSE_MIN_BYTES;
+}
+
+// y = [res +] SiLU(conv3x3(SiLU(conv3x3(x, W1) + bias1), W2) + bias2) in one launch, 32 channels throughout, W % 4 == 0,
+// bit-identical to yolosod_conv3x3_silu_xs twice: image b of x / y / res ([32][H][W], 16-byte aligned) at x + b
+// x_bstride / y + b y_bstride / res + b res_bstride (channel slices of a concat buffer); res NULL: no shortcut; prep1 /
+// prep2: the two convs' blocks of yolosod_conv3x3_prepare_ex(w, 32, 32, ...). y must not alias x or res. This entry
+// always runs the fused kernel; callers route with yolosod_debug_bottleneck3x3_fused.
+YS_EXPORT int yolosod_bottleneck3x3_silu_xs(const float* x, long x_bstride, float* y, long y_bstride, const float* res,
+                                            long res_bstride, int B, int H, int W, const float* bias1,
+                                            const void* prep1, size_t prep1_bytes, const float* bias2,
+                                            const void* prep2, size_t prep2_bytes, void* stream) {
+  YS_CHECK_ARG(x && y && bias1 && bias2 && prep1 && prep2, "bottleneck3x3: null pointer");
+  YS_CHECK_ARG(B >= 0 && H > 0 && W > 0 && W % 4 == 0, "bottleneck3x3: bad shape (W %% 4 == 0 only)");
+  YS_CHECK_ARG(32L * H * W * 4 < (1L << 31), "bottleneck3x3: plane too large");
+  const long img = 32L * H * W;
+  YS_CHECK_ARG(x_bstride >= img && y_bstride >= img && (!res || res_bstride >= img),
+               "bottleneck3x3: batch stride below %ld", img);
+  YS_CHECK_ARG(((uintptr_t)x & 15) == 0 && x_bstride % 4 == 0 && ((uintptr_t)y & 15) == 0 && y_bstride % 4 == 0 &&
+                   (!res || (((uintptr_t)res & 15) == 0 && res_bstride % 4 == 0)),
+               "bottleneck3x3: images not 16-byte aligned");
+  if (B == 0) return 0;
+  h16_t *wp1, *wp2;
+  unsigned *flag1, *flag2;
+  YS_CHECK_ARG(conv3x3_carve(const_cast<void*>(prep1), prep1_bytes, 32, 32, &wp1, &flag1) &&
+                   conv3x3_carve(const_cast<void*>(prep2), prep2_bytes, 32, 32, &wp2, &flag2),
+               "bottleneck3x3: prepared block too small");
+  c3::BnArgs a{x, x_bstride, y, y_bstride, res, res_bstride, wp1, wp2, bias1, bias2, H, W, (W + c3::TW - 1) / c3::TW,
+               (H + c3::TH - 1) / c3::TH, 0, range_flag_dev(), flag1, flag2};
+  const long ntiles = (long)B * a.tiles_x * a.tiles_y;
+  YS_CHECK_ARG(ntiles < (1L << 31), "bottleneck3x3: too many tiles");
+  a.ntiles = (int)ntiles;
+  const long slots = c3_cu_count();  // one workgroup per CU (LDS)
+  long grid = slots < (ntiles + 7) / 8 * 8 ? slots : (ntiles + 7) / 8 * 8;
+  grid = (grid + 7) / 8 * 8;
+  hipStream_t st = (hipStream_t)stream;
+  if (res)
+    hipLaunchKernelGGL(c3::bottleneck3x3_c32_kernel<true>, dim3((unsigned)grid), dim3(c3::BN_NT), 0, st, a);
+  else
+    hipLaunchKernelGGL(c3::bottleneck3x3_c32_kernel<false>, dim3((unsigned)grid), dim3(c3::BN_NT), 0, st, a);
+  YS_CHECK_LAUNCH("bottleneck3x3");
+  return 0;
 }
 
 // 3x3 / stride 1 / pad 1 conv with 64 outputs, contiguous y [B][64][H][W].

@@ -202,6 +202,21 @@ SPPF_HIP = os.environ.get("YOLOSOD_SPPF_HIP", "1") != "0"
 STEM_HIP = os.environ.get("YOLOSOD_STEM_HIP", "1") != "0"
 
 
+def _onoff_switch(name: str, value: str) -> bool:
+    """A 0 / 1 switch from its environment spelling; anything else is an error, as with the backbone switches."""
+    v = value.strip()
+    if v not in ("0", "1"):
+        raise ValueError(f"{name}={value!r}: expected 0 or 1")
+    return v == "1"
+
+
+# the 32-channel Bottlenecks of the two P2 C2fs (layers 3 and 27: 32 -> 32 -> 32 at 160^2) as one launch that keeps
+# the intermediate map in LDS (csrc/conv3x3.hip, bottleneck3x3_c32_kernel), bit-identical to the two conv launches;
+# taken when both convs are on the stride-1 fp16-split kernel and the library says the map is large enough for the
+# launch to pay (yolosod_debug_bottleneck3x3_fused, DESIGN 24). YOLOSOD_BOTTLENECK_FUSE=0: always the two launches
+BOTTLENECK_FUSE = _onoff_switch("YOLOSOD_BOTTLENECK_FUSE", os.environ.get("YOLOSOD_BOTTLENECK_FUSE", "1"))
+
+
 def _s2_on(s2, layer=None):
     """Whether a Conv's stride-2 mark (False / True: neck / "backbone") routes it to the stride-2 fp16-split kernel.
     S2_BACKBONE is False, True (tests set these: none / all of the marked convs) or a frozenset of layer indices;
@@ -434,7 +449,30 @@ class Bottleneck(nn.Module):
         self.cv2 = Conv(c_, c2, k[1], 1, g=g)
         self.add = shortcut and c1 == c2
 
+    def _one_launch(self, x, out, out2) -> bool:
+        """Both convs would run on the stride-1 fp16-split kernel (conv_epilogue's ``s1`` route), 32 channels
+        throughout, fp32, and the library takes the shape as the fused launch."""
+        if not (BOTTLENECK_FUSE and out2 is None and x.device.type == "cuda" and x.dtype == torch.float32
+                and _hip.split_convs_enabled() and x.dim() == 4 and x.shape[1] == 32 and x.shape[3] % 4 == 0):
+            return False
+        for cv in (self.cv1, self.cv2):
+            c = cv.conv
+            if not (cv.is_fused() and c.bias is not None and _act_code(cv.act) == 1 and cv.emit_stats is None
+                    and _s1_on(cv.s1_mark()) and c.in_channels == 32 and c.out_channels == 32
+                    and _hip.conv3x3_ok(x, c)):
+                return False
+        if not _hip._imgs_contig(x) or (out is not None and not _hip._imgs_contig(out)):
+            return False
+        return _hip.bottleneck3x3_fused(x.shape[0], x.shape[2], x.shape[3])
+
     def forward(self, x, out=None, out2=None):
+        if self._one_launch(x, out, out2):
+            c1, c2 = self.cv1.conv, self.cv2.conv
+            prep1 = lambda: _cached(c1, "c3prep", (c1.weight,), lambda: _hip.conv3x3_prepare(c1.weight))  # noqa: E731
+            prep2 = lambda: _cached(c2, "c3prep", (c2.weight,), lambda: _hip.conv3x3_prepare(c2.weight))  # noqa: E731
+            backbone = self.cv2.s1_mark() == "backbone"
+            return _hip.bottleneck3x3_silu(x, c1.bias, prep1, c2.bias, prep2, out=out, res=x if self.add else None,
+                                           op="bottleneck3x3_backbone" if backbone else "bottleneck3x3")
         if self.cv2.is_fused():  # shortcut fused into cv2's epilogue, output optionally into a concat slice
             return self.cv2.forward_fuse(self.cv1(x), out=out, res=x if self.add else None, out2=out2)
         y = x + self.cv2(self.cv1(x)) if self.add else self.cv2(self.cv1(x))
