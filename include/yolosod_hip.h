@@ -416,6 +416,15 @@ int yolosod_conv1x1x2_silu(const float* x, long x_bstride, float* y, long y_bstr
 int yolosod_conv1x1x2_silu_cat(const float* x, long x_bstride, const float* x2, long x2_bstride, int k1, float* y,
                                long y_bstride, float* y2, long y2_bstride, int c2lo, int B, int cin, int cout, int HW,
                                const float* bias, const void* prep, size_t prep_bytes, int up_w, void* stream);
+/* yolosod_conv1x1x2_silu (one input, no y2) that also emits y's per-plane statistics for the SE (stats 1: sums) / CBAM
+ * (stats 2: sums and maxes, pmax required) gate that follows, from the values as its epilogue stores them: psum /
+ * pmax[B*cout*parts] in the layout of yolosod_se_forward_pre / yolosod_cbam_forward_pre (parts =
+ * yolosod_plane_parts(HW); k = 0 holds the plane's total, k > 0 hold 0 / -inf). tile_ws: 2*B*cout*ceil(HW/64) floats.
+ * No atomics: deterministic, independent of B. y is bit-identical to yolosod_conv1x1x2_silu's. The forced group field
+ * of yolosod_debug_set_conv1x1x2_form holds; the statistics forms have one pair of staged planes. */
+int yolosod_conv1x1x2_silu_stats(const float* x, long x_bstride, float* y, long y_bstride, int B, int cin, int cout,
+                                 int HW, const float* bias, const void* prep, size_t prep_bytes, int stats, int parts,
+                                 float* psum, float* pmax, float* tile_ws, void* stream);
 /* Test / measurement hook: force the form of the fp16-split 1x1 conv kernel (csrc/conv1x1x2.hip); every form gives
  * bit-identical results. form = groups + 4 * buffers. groups: 0 automatic, 1 workgroups of 128 output channels (two
  * 16-channel blocks per wave), 2 of 256 (four blocks per wave; Cout % 256 == 0, any other Cout runs groups 1).

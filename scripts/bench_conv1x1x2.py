@@ -104,8 +104,55 @@ def forms():
                 lib.yolosod_debug_set_conv1x1x2_form(0)
 
 
+def stats():
+    """python scripts/bench_conv1x1x2.py stats: the three gate-feeding neck convs of the n640 step at bs 32 (cv2 of the
+    C2fs L17 / L22 / L31) - the new launch (yolosod_conv1x1x2_silu_stats; before the CA: the plain launch, and the CA
+    pooling the map itself) against the sequence it replaces, F.conv2d + bias_act(stats=...), under
+    cudnn.deterministic. The L31 pair is timed with the CA_Block's own launch behind it on both sides, since the pool
+    moves into that launch. Each side twice per run; run it twice. A layer is kept only if every timing of the new form
+    beats every timing of the old sequence by more than the spread (the largest difference between two timings of one
+    side on one shape)."""
+    dev = torch.device("cuda")
+    torch.backends.cudnn.deterministic = True
+    g = torch.Generator().manual_seed(0)
+    spread = 0.0
+    rows = []
+    with torch.inference_mode():
+        for layer, cin, cout, side, st in ((17, 384, 256, 40, "summax"), (22, 192, 128, 80, "sum"),
+                                           (31, 192, 128, 80, "capool")):
+            B = 32
+            x = torch.randn(B, cin, side, side, device=dev)
+            w = (torch.randn(cout, cin, 1, 1, generator=g) * (1.0 / cin ** 0.5)).to(dev)
+            b = (torch.randn(cout, generator=g) * 0.1).to(dev)
+            blk = _hip.conv1x1x2_prepare(w)
+            out = torch.empty((B, cout, side, side), device=dev)
+            tail = lambda y: y  # noqa: E731
+            if st == "capool":
+                mip = max(8, cout // 32)
+                cw = lambda *s: (torch.randn(*s, generator=g) * 0.1).to(dev)  # noqa: E731
+                ca = (cw(mip, cout, 1, 1), cw(mip), torch.ones(mip, device=dev), cw(mip), cw(mip),
+                      torch.ones(mip, device=dev), 1e-5, cw(cout, mip, 1, 1), cw(cout), cw(cout, mip, 1, 1), cw(cout))
+                tail = lambda y: _hip.ca_forward(y, *ca)  # noqa: E731
+            old = lambda: tail(_hip.bias_act(F.conv2d(x, w), b, 1, out=out, stats=st))  # noqa: E731
+            new = lambda: tail(_hip.conv1x1x2_silu(x, b, lambda: blk, cout, out=out, stats=st))  # noqa: E731
+            to, tn = [], []
+            for _ in range(2):
+                to.append(timeit(old, iters=50))
+                tn.append(timeit(new, iters=50))
+            spread = max(spread, max(to) - min(to), max(tn) - min(tn))
+            rows.append((layer, cin, cout, side, st, to, tn))
+    for layer, cin, cout, side, st, to, tn in rows:
+        keep = min(to) - max(tn) > spread
+        print(f"L{layer} {cin:4d} -> {cout:4d} at {side}^2 {st:7s}  old {min(to):.4f} - {max(to):.4f} ms  "
+              f"new {min(tn):.4f} - {max(tn):.4f} ms  {'KEEP' if keep else 'no gain'}"
+              + ("  (with the CA launch on both sides)" if st == "capool" else ""), flush=True)
+    print(f"spread {spread:.4f} ms")
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "forms":
         forms()
+    elif len(sys.argv) > 1 and sys.argv[1] == "stats":
+        stats()
     else:
         main()

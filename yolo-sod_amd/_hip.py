@@ -81,6 +81,7 @@ SIGNATURES = {
     "yolosod_conv1x1x2_silu": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "yolosod_conv1x1x2_silu_cat": (_i, [_vp, _l, _vp, _l, _i, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _sz,
                                         _i, _vp]),
+    "yolosod_conv1x1x2_silu_stats": (_i, [_vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _vp, _sz, _i, _i, _vp, _vp, _vp, _vp]),
     "yolosod_sppf_pool": (_i, [_vp, _l, _i, _i, _i, _i, _vp]),
     "yolosod_conv1x1_thin_cat": (_i, [_vp, _l, _vp, _l, _i, _vp, _vp, _vp, _l, _vp, _l, _i, _i, _i, _i, _l, _i, _vp]),
     "yolosod_conv3x3_prep_bytes_ex": (_sz, [_i, _i]),
@@ -1029,12 +1030,18 @@ def conv1x1x2_prepare(w):
     return blk
 
 
-def conv1x1x2_silu(x, bias, prep, cout, out=None, out2=None, c2lo=0, op="conv1x1x2"):
+def conv1x1x2_silu(x, bias, prep, cout, out=None, out2=None, c2lo=0, op="conv1x1x2", stats=None):
     """SiLU(W x + bias) for a 1x1 conv on the fp16 two-term split MFMA (csrc/conv1x1x2.hip). ``x``, ``out`` may be
     channel slices of concat buffers (contiguous images); ``out2``: channels [c2lo, Cout) stored again (packed);
-    ``op``: the op_timer key's name (the backbone's launches are recorded as "conv1x1x2_backbone")."""
+    ``op``: the op_timer key's name (the backbone's launches are recorded as "conv1x1x2_backbone").
+    ``stats`` ("sum" / "summax"): the same launch emits the output's plane statistics for the SE / CBAM gate that
+    follows (yolosod_conv1x1x2_silu_stats), attached as ``_ys_plane_stats`` (PlaneStats) the way bias_act(stats=...)
+    attaches them; "capool": the plain launch - the CA_Block that follows pools the finished output itself. These
+    launches are recorded as ("conv1x1x2_stats", x.shape, (cout, stats)) and take no out2 and no CatView."""
     lib = load_library()
     B, Cin, H, W = x.shape
+    if stats is not None and (stats not in ("sum", "summax", "capool") or out2 is not None or isinstance(x, CatView)):
+        raise RuntimeError(f"conv1x1x2: stats={stats!r} takes one input tensor, no out2")
     if out is None:
         y = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
     else:
@@ -1043,6 +1050,24 @@ def conv1x1x2_silu(x, bias, prep, cout, out=None, out2=None, c2lo=0, op="conv1x1
     if out2 is not None:
         _img_view(out2, (B, cout - c2lo, H, W), "conv1x1x2: out2")
     b = bias.detach().float().contiguous()
+    if stats in ("sum", "summax"):
+        HW = H * W
+        parts, _ = plane_parts(HW)
+        psum = torch.empty(B * cout * parts, dtype=torch.float32, device=x.device)
+        pmax = torch.empty_like(psum) if stats == "summax" else None
+        tws = torch.empty(2 * B * cout * ((HW + 63) // 64), dtype=torch.float32, device=x.device)
+
+        def run_stats():
+            blk = prep()
+            return lib.yolosod_conv1x1x2_silu_stats(x.data_ptr(), x.stride(0), y.data_ptr(), y.stride(0), B, Cin, cout,
+                                                    HW, _dev(b, "bias"), blk.data_ptr(), blk.numel(),
+                                                    2 if stats == "summax" else 1, parts, psum.data_ptr(),
+                                                    None if pmax is None else pmax.data_ptr(), tws.data_ptr(),
+                                                    _stream(x.device))
+
+        _check(_launch(("conv1x1x2_stats", tuple(x.shape), (cout, stats)), x.device, run_stats), "conv1x1x2_stats")
+        y._ys_plane_stats = PlaneStats(psum, pmax, parts, y.shape)
+        return y
 
     x0, x1 = x.parts if isinstance(x, CatView) else (x, None)
 
@@ -1056,6 +1081,8 @@ def conv1x1x2_silu(x, bias, prep, cout, out=None, out2=None, c2lo=0, op="conv1x1
                                               W if x1 is not None and x.up0 else 0, _stream(x.device))
 
     extra = (cout, out2 is not None) + (("cat",) if x1 is not None else ())
+    if stats == "capool":
+        op, extra = "conv1x1x2_stats", (cout, stats)
     _check(_launch((op, tuple(x.shape), extra), x.device, run), "conv1x1x2")
     return y
 

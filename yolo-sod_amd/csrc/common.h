@@ -290,4 +290,9 @@ __device__ __forceinline__ f32x4 mfma_f16x3(f16x8_t ah, f16x8_t al, f16x8_t bh, 
 // are identical either way (each workgroup's work and summation order is unchanged).
 static inline int mall_reverse() { return 1; }
 
+// host (conv_epilogue.hip): per-plane totals of 64-pixel tile partials tsum / tmax[plane * ntile + tile] (tmax may be
+// NULL with pmax) as psum / pmax[plane * parts + k], k = 0 the total, k > 0 0 / -inf: the layout the SE / CBAM gates read
+void thin_stats_reduce_launch(const float* tsum, const float* tmax, long planes, int ntile, int parts, float* psum,
+                              float* pmax, hipStream_t st);
+
 }  // namespace ys

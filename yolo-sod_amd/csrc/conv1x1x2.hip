@@ -19,6 +19,12 @@
 // == 0: the x tile is staged and split once per 256 channels and every pair of LDS reads feeds 12 MFMAs), and the two
 // planes may be double-buffered (stage s + 1 is split and written while other waves still run stage s's MFMAs: one
 // barrier per stage instead of two, 69632 B of LDS, still two workgroups per CU).
+//
+// Statistics forms (STATS 1: sum, 2: sum and max; yolosod_conv1x1x2_silu_stats): a conv whose output feeds an SE / CBAM
+// gate also emits, per (plane, 64-pixel tile), the sum (and max) of the values exactly as it stores them, from the
+// registers the epilogue holds; thin_stats_reduce_kernel (conv_epilogue.hip) adds a plane's tiles in a fixed order
+// into the PlaneStats layout the gates read. No atomics: deterministic and independent of the batch size. Everything
+// up to the store is the STATS 0 code, so the stored output is bit-identical to it.
 #include "common.h"
 
 namespace ys {
@@ -47,176 +53,13 @@ struct Args {
   int up_w;            // != 0 (with x2): x is the quarter-size source [k1][H/2][up_w/2] of a nearest 2x upsample to
                        // [k1][H][up_w], read in place at (y >> 1, x >> 1)
 };
+// STATS forms (no second store): y2 = the per-tile partial sums [(b Cout + channel) ntile + tile], y2 + y2bs = the
+// partial maxes in the same layout (STATS 2). The struct stays as it is so that the other instances keep their code.
 
-// NP pixels per tile (64 or 128: the weights are read from L2 once per tile, 128 halves that traffic)
-// CPW: 16-channel output blocks per wave (2: workgroups of 128 output channels; 4: of 256; 1: of 64, for Cout 64)
-// DB: the staged planes are double-buffered (one barrier per stage)
-template <bool DUAL, int NP, int CPW = 2, bool DB = false>
-__global__ __launch_bounds__(NT, 2) void conv1x1_x2_kernel(Args p) {
-  constexpr int PL = NP * PS;           // plane (halves)
-  constexpr int NITEM = (KS / 4) * NP;  // (channel quad, pixel) items per stage
-  constexpr int NIT = NITEM / NT;
-  constexpr int NPB = NP / 16;          // pixel blocks
-  static_assert(NITEM % NT == 0, "items");
-  __shared__ __attribute__((aligned(16))) h16_t Pl[(DB ? 4 : 2) * PL];
-  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int l15 = lane & 15, g = lane >> 4;
-  const int ngrp = p.cout / (64 * CPW);
-  const int grp = blockIdx.x % ngrp, tile = (blockIdx.x / ngrp) % p.ntile, b = blockIdx.x / (ngrp * p.ntile);
-  const int HW = p.HW, p0 = tile * NP, nst = (p.cin + KS - 1) / KS, nks = nst * (KS / 32);  // weights padded to KS
-  float rng = 0.f;
-
-  auto rsrc = [&](const void* base, unsigned bytes) {
-    const unsigned long long a = (unsigned long long)base;
-    return __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(a >> 32)) << 32) |
-                (unsigned)__builtin_amdgcn_readfirstlane((unsigned)a)),
-        (short)0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-  };
-  // the part of a virtual concat a stage reads (stages from k1 / KS on: x2) as a buffer resource built from scalars
-  // per stage (a select between two resource values is lowered to VGPRs, and every load then runs a waterfall loop)
-  const float* xb1 = p.x + (long)b * p.xbs;
-  const float* xb2 = p.x2 ? p.x2 + (long)b * p.x2bs : xb1;
-  // the first part's plane: HW floats, or the HW / 4 of the quarter-size source it is the nearest 2x upsample of
-  const int HW1 = p.up_w ? HW >> 2 : HW;
-  const unsigned nb1 = (unsigned)((long)p.k1 * HW1 * 4), nb2 = (unsigned)((long)(p.cin - p.k1) * HW * 4);
-  const __amdgpu_buffer_rsrc_t rw = rsrc(p.wp, (unsigned)((long)nks * (p.cout >> 4) * 2 * 1024));
-
-  // staging item e = tid + NT i: channel quad e / NP = q0 + (NT / NP) i (channels 4 quad .. + 3 of the stage), pixel
-  // e % NP = tid % NP (clamped to the image: pixels past HW load the last pixel, their outputs are not stored)
-  static_assert(NT % NP == 0, "a thread stages one pixel");
-  const int q0 = tid / NP;
-  const int pc = min(p0 + tid % NP, HW - 1);
-  int pc1 = pc;  // the pixel's offset in a first-part plane: its source pixel (y >> 1, x >> 1) when that part is upsampled
-  if (p.up_w) {
-    const int yy = pc / p.up_w, xx = pc - yy * p.up_w;
-    pc1 = (yy >> 1) * (p.up_w >> 1) + (xx >> 1);
-  }
-  f32x4 sv[NIT];
-  // the stage / channel offset is in the per-lane offset, so the buffer range check covers it: channels past Cin
-  // (the last stage of a Cin that is not a multiple of KS) read 0, as do the padded weights they meet
-  auto load_part = [&](int st, int k0, int k1, bool live) __attribute__((always_inline)) {
-    const bool second = KS * st >= p.k1;  // stage-uniform
-    const int chs = second ? HW : HW1;    // plane stride of the part (scalar)
-    const unsigned sx = (unsigned)((second ? KS * st - p.k1 : KS * st) * chs * 4);
-    const unsigned vo = (unsigned)((4 * q0 * chs + (second ? pc : pc1)) * 4);
-    // !live: an empty range (the last stage's "next stage" loads return 0 at once)
-    const __amdgpu_buffer_rsrc_t r = rsrc(second ? xb2 : xb1, live ? (second ? nb2 : nb1) : 0u);
-#pragma unroll
-    for (int k = 0; k < 4 * NIT; ++k)
-      if (k >= k0 && k < k1)
-        sv[k >> 2][k & 3] = __builtin_bit_cast(
-            float, __builtin_amdgcn_raw_buffer_load_b32(
-                       r, vo + sx + (unsigned)((4 * (NT / NP) * (k >> 2) + (k & 3)) * chs * 4), 0, 0));
-  };
-  // weight fragments of k step s (global), channel blocks cb0 + u, planes 0 / 1
-  const int cb0 = grp * 4 * CPW + CPW * wid;
-  auto wfrag = [&](int s, int u, int pl) __attribute__((always_inline)) {
-    const int st = __builtin_amdgcn_readfirstlane((s * (p.cout >> 4) * 2) * 1024);
-    return __builtin_bit_cast(f16x8_t, __builtin_amdgcn_raw_buffer_load_b128(
-                                           rw, (unsigned)((((cb0 + u) * 2 + pl) * 64 + lane) * 16), st, 0));
-  };
-  f32x4 acc[CPW][NPB];
-#pragma unroll
-  for (int u = 0; u < CPW; ++u)
-#pragma unroll
-    for (int k = 0; k < NPB; ++k) acc[u][k] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float bo[CPW];  // loaded before the loop: an epilogue load would wait behind every load in flight
-#pragma unroll
-  for (int u = 0; u < CPW; ++u) bo[u] = p.bias[16 * (cb0 + u) + l15];
-
-  // the loaded stage, split, as the two planes at pl
-  auto stage_store = [&](h16_t* pl) __attribute__((always_inline)) {
-#pragma unroll
-    for (int i = 0; i < NIT; ++i) {
-      const int e = tid + NT * i, quad = e / NP, px = e - quad * NP;
-      uint2 hh, ll;
-      split4x(sv[i], hh, ll);
-      rng = range_acc(rng, sv[i]);
-      h16_t* d = pl + px * PS + 4 * quad;
-      *reinterpret_cast<uint2*>(d) = hh;
-      *reinterpret_cast<uint2*>(d + PL) = ll;
-    }
-  };
-  load_part(0, 0, 4 * NIT, true);
-  if (DB) {
-    stage_store(Pl);
-    __syncthreads();
-  }
-  for (int st = 0; st < nst; ++st) {
-    // DB: stage st is in plane pair st & 1 (written during stage st - 1, behind that stage's barrier)
-    const h16_t* cur = DB ? Pl + (st & 1) * 2 * PL : Pl;
-    if (!DB) {
-      __syncthreads();  // every wave is done with the previous stage's planes
-      stage_store(Pl);
-      __syncthreads();
-    }
-    const bool nlive = st + 1 < nst;
-    const int stn = nlive ? st + 1 : st;
-    f16x8_t wa[CPW][2], wn[CPW][2];
-#pragma unroll
-    for (int u = 0; u < CPW; ++u) {
-      wa[u][0] = wfrag(4 * st, u, 0);
-      wa[u][1] = wfrag(4 * st, u, 1);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int kk = 0; kk < KS / 32; ++kk) {
-      const int sn = kk + 1 < KS / 32 ? 4 * st + kk + 1 : 4 * st + kk;  // one k step ahead (unconditional)
-#pragma unroll
-      for (int u = 0; u < CPW; ++u) {
-        wn[u][0] = wfrag(sn, u, 0);
-        wn[u][1] = wfrag(sn, u, 1);
-      }
-      load_part(stn, NIT * kk, NIT * kk + NIT, nlive);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int k = 0; k < NPB; ++k) {
-        const h16_t* src = cur + (16 * k + l15) * PS + 32 * kk + 8 * g;
-        const f16x8_t xh = *reinterpret_cast<const f16x8_t*>(src);
-        const f16x8_t xl = *reinterpret_cast<const f16x8_t*>(src + PL);
-#pragma unroll
-        for (int u = 0; u < CPW; ++u) {
-          f32x4 c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wa[u][1], acc[u][k], 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xl, wa[u][0], c, 0, 0, 0);
-          acc[u][k] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wa[u][0], c, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < CPW; ++u) {
-        wa[u][0] = wn[u][0];
-        wa[u][1] = wn[u][1];
-      }
-    }
-    if (DB && nlive) {
-      // the other pair's last readers were stage st - 1's MFMAs, all done before the barrier that ended that stage;
-      // this barrier publishes stage st + 1 and ends the reads of stage st's pair, which stage st + 1 overwrites
-      stage_store(Pl + ((st + 1) & 1) * 2 * PL);
-      __syncthreads();
-    }
-  }
-  // epilogue: lane (g, l15) of (u, pixel block k) holds channel 16 (cb0 + u) + l15, pixels 16 k + 4 g .. + 3
-  float* yb = p.y + (long)b * p.ybs;
-#pragma unroll
-  for (int u = 0; u < CPW; ++u) {
-    const int o = 16 * (cb0 + u) + l15;
-#pragma unroll
-    for (int k = 0; k < NPB; ++k) {
-      const int px = p0 + 16 * k + 4 * g;
-      f32x4 v;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] = silu_fast_(acc[u][k][j] * (1.0f / WSC) + bo[u]);
-      if (px < HW) {  // HW % 4 == 0: 4 pixels all in or all out
-        __builtin_nontemporal_store(v, reinterpret_cast<f32x4*>(yb + (long)o * HW + px));
-        if (DUAL && o >= p.c2lo)
-          __builtin_nontemporal_store(
-              v, reinterpret_cast<f32x4*>(p.y2 + (long)b * p.y2bs + (long)(o - p.c2lo) * HW + px));
-      }
-    }
-  }
-  range_report(p.range_flag, rng);
-  if (p.prep_flag && p.range_flag && blockIdx.x == 0 && threadIdx.x == 0 && *p.prep_flag) *p.range_flag = 1u;
-}
+#include "conv1x1x2_kernel.h"
+#define YS_C1_STATS_FORMS
+#include "conv1x1x2_kernel.h"
+#undef YS_C1_STATS_FORMS
 
 // W [Cout][Cin] -> fragment-major planes of 64 W: one thread per (output channel, input channel)
 __global__ __launch_bounds__(256) void conv1x1_prep_kernel(const float* __restrict__ w, int cin, int cin_pad,
@@ -388,4 +231,52 @@ YS_EXPORT int yolosod_conv1x1x2_silu(const float* x, long x_bstride, float* y, l
                                      const void* prep, size_t prep_bytes, void* stream) {
   return yolosod_conv1x1x2_silu_cat(x, x_bstride, nullptr, 0, cin, y, y_bstride, y2, y2_bstride, c2lo, B, cin, cout, HW,
                                     bias, prep, prep_bytes, 0, stream);
+}
+
+// yolosod_conv1x1x2_silu (one input, no second store) that also emits the output's per-plane statistics for the SE
+// (stats 1: sums) / CBAM (stats 2: sums and maxes) gate that follows, in the psum / pmax[B*cout*parts] layout of
+// yolosod_se_forward_pre / yolosod_cbam_forward_pre (parts = yolosod_plane_parts(HW)): k = 0 holds the plane's total,
+// k > 0 hold 0 / -inf. tile_ws: 2 * B * cout * ceil(HW / 64) floats. The stored y is bit-identical to
+// yolosod_conv1x1x2_silu's. Cout a multiple of 128; the forced group field of yolosod_debug_set_conv1x1x2_form holds,
+// the statistics forms have one pair of staged planes.
+template <int CPW>
+static void c1_launch_stats(int stats, unsigned nwg, hipStream_t st, const c1::Args& a) {
+  if (stats == 2)
+    hipLaunchKernelGGL((c1::conv1x1_x2s_kernel<CPW, 2>), dim3(nwg), dim3(c1::NT), 0, st, a);
+  else
+    hipLaunchKernelGGL((c1::conv1x1_x2s_kernel<CPW, 1>), dim3(nwg), dim3(c1::NT), 0, st, a);
+}
+
+YS_EXPORT int yolosod_conv1x1x2_silu_stats(const float* x, long x_bstride, float* y, long y_bstride, int B, int cin,
+                                           int cout, int HW, const float* bias, const void* prep, size_t prep_bytes,
+                                           int stats, int parts, float* psum, float* pmax, float* tile_ws,
+                                           void* stream) {
+  YS_CHECK_ARG(x && y && bias && prep && psum && tile_ws, "conv1x1x2_stats: null pointer");
+  YS_CHECK_ARG((stats == 1 || stats == 2) && (stats == 1 || pmax) && parts >= 1, "conv1x1x2_stats: stats=%d parts=%d",
+               stats, parts);
+  YS_CHECK_ARG(B >= 0 && HW > 0 && HW % 4 == 0 && cout % 128 == 0 && yolosod_conv1x1x2_prep_bytes(cin, cout) > 0,
+               "conv1x1x2_stats: bad shape");
+  YS_CHECK_ARG(x_bstride >= (long)cin * HW && y_bstride >= (long)cout * HW, "conv1x1x2_stats: batch strides too small");
+  YS_CHECK_ARG((long)c1_pad(cin) * HW * 4 < (1L << 32), "conv1x1x2_stats: image too large for 32-bit buffer offsets");
+  YS_CHECK_ARG(((uintptr_t)y & 15) == 0 && y_bstride % 4 == 0, "conv1x1x2_stats: output must be 16-byte aligned");
+  if (B == 0) return 0;
+  h16_t* wp;
+  unsigned* flag;
+  YS_CHECK_ARG(c1_carve(const_cast<void*>(prep), prep_bytes, cin, cout, &wp, &flag),
+               "conv1x1x2_stats: prepared block too small");
+  const int ntile = (HW + 63) / 64;
+  float* tsum = tile_ws;
+  float* tmax = tile_ws + (long)B * cout * ntile;
+  c1::Args a{x, x_bstride, wp, bias, y, y_bstride, tsum, tmax - tsum, 0, cin, cout, HW, ntile, range_flag_dev(), flag,
+             nullptr, 0, cin, 0};
+  const bool g256 = (c1_form(B, cout, HW) & 3) == 2;
+  const long nwg = (long)B * ntile * (cout / (g256 ? 256 : 128));
+  YS_CHECK_ARG(nwg < (1L << 31), "conv1x1x2_stats: too many tiles");
+  hipStream_t st = (hipStream_t)stream;
+  if (g256) c1_launch_stats<4>(stats, (unsigned)nwg, st, a);
+  else c1_launch_stats<2>(stats, (unsigned)nwg, st, a);
+  thin_stats_reduce_launch(tsum, stats == 2 ? tmax : nullptr, (long)B * cout, ntile, parts, psum,
+                           stats == 2 ? pmax : nullptr, st);
+  YS_CHECK_LAUNCH("conv1x1x2_stats");
+  return 0;
 }

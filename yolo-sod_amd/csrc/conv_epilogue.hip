@@ -396,7 +396,7 @@ __global__ __launch_bounds__(256) void thin_stats_reduce_kernel(const float* __r
   float s = 0.f, m = -INFINITY;
   for (int t = lane; t < ntile; t += 64) {
     s += tsum[plane * ntile + t];
-    m = fmaxf(m, tmax[plane * ntile + t]);
+    if (tmax) m = fmaxf(m, tmax[plane * ntile + t]);
   }
   s = wave_sum(s);
   m = wave_max(m);
@@ -404,6 +404,13 @@ __global__ __launch_bounds__(256) void thin_stats_reduce_kernel(const float* __r
     psum[plane * parts + k] = k == 0 ? s : 0.f;
     if (pmax) pmax[plane * parts + k] = k == 0 ? m : -INFINITY;
   }
+}
+
+// the reduce for another file's tile partials (csrc/conv1x1x2.hip's statistics forms); tmax / pmax NULL: sums only
+void thin_stats_reduce_launch(const float* tsum, const float* tmax, long planes, int ntile, int parts, float* psum,
+                              float* pmax, hipStream_t st) {
+  hipLaunchKernelGGL(thin_stats_reduce_kernel, dim3((unsigned)((planes + 3) / 4)), dim3(256), 0, st, tsum, tmax, planes,
+                     ntile, parts, psum, pmax);
 }
 
 // Nearest 2x upsample (nn.Upsample(scale_factor=2, mode='nearest'), conv.py / tasks.py neck rows) straight into a

@@ -191,6 +191,16 @@ N1_NECK = os.environ.get("YOLOSOD_N1_NECK", "1") != "0"
 N1_BACKBONE_DEFAULT = "8,11,13"
 N1_BACKBONE_LAYERS = (6, 8, 11, 13)
 N1_BACKBONE = _backbone_switch(os.environ.get("YOLOSOD_N1_BACKBONE", N1_BACKBONE_DEFAULT), N1_BACKBONE_LAYERS)
+# the neck's wide 1x1 convs whose output feeds a gate directly (cv2 of the C2fs L17 -> CBAM L18, L22 -> SE L23,
+# L31 -> CA L32 at the paper scale; Conv.n1_stats_layer) on the same kernel's statistics forms, which emit the SE /
+# CBAM plane statistics from the registers of the conv's epilogue (yolosod_conv1x1x2_silu_stats), instead of MIOpen's
+# fp32 GEMM + the bias / SiLU / statistics pass; before a CA the plain launch runs and the CA pools the finished map
+# itself. YOLOSOD_N1_STATS = 0 / 1 / a comma list of those layers. False, True or a frozenset, as N1_BACKBONE.
+# Default: all three. Every candidate set passes tests/test_gpu_e2e.py unedited (noisy worst box px
+# 0.138 - 0.146 against 0.143 with none routed, bound 0.158), and the full set is the fastest in the step.
+N1_STATS_DEFAULT = "17,22,31"
+N1_STATS_LAYERS = (17, 22, 31)
+N1_STATS = _backbone_switch(os.environ.get("YOLOSOD_N1_STATS", N1_STATS_DEFAULT), N1_STATS_LAYERS)
 # the neck C2fs' Bottlenecks (stride-1 fp16-split kernel) read their inputs as slices of the C2f buffer instead of
 # packed copies written by a second store (YOLOSOD_C2F_SLICES=0: the dual-store form)
 C2F_SLICES = os.environ.get("YOLOSOD_C2F_SLICES", "1") != "0"
@@ -249,15 +259,25 @@ def _n1_on(n1, layer=None):
     return layer in N1_BACKBONE
 
 
-def _n1_run(conv, x, out, out2, c2lo, n1):
+def _n1_stats_on(stats_layer) -> bool:
+    """Whether a gate-feeding wide 1x1 conv of the neck (Conv.n1_stats_layer, the index of its layer) runs on the
+    fp16-split 1x1 kernel with its statistics. N1_STATS is False, True or a frozenset of layer indices."""
+    if stats_layer is None:
+        return False
+    if isinstance(N1_STATS, bool):
+        return N1_STATS
+    return stats_layer in N1_STATS
+
+
+def _n1_run(conv, x, out, out2, c2lo, n1, stats=None):
     """The fp16-split 1x1 kernel on a conv that conv_epilogue routed to it."""
     prep = lambda: _cached(conv, "c1prep", (conv.weight,), lambda: _hip.conv1x1x2_prepare(conv.weight))  # noqa: E731
     return _hip.conv1x1x2_silu(x, conv.bias, prep, conv.out_channels, out=out, out2=out2, c2lo=c2lo,
-                               op="conv1x1x2_backbone" if n1 == "backbone" else "conv1x1x2")
+                               op="conv1x1x2_backbone" if n1 == "backbone" else "conv1x1x2", stats=stats)
 
 
 def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, out2=None, c2lo=0, tower=False,
-                  s2=False, s1=False, n1=False, layer=None):
+                  s2=False, s1=False, n1=False, layer=None, stats_layer=None):
     """GPU fast path of ``act(conv(x)) (+ res)``: MIOpen conv without bias, then one HIP pass for bias +
     activation (+ shortcut), optionally written straight into a channel slice ``out`` of a concat buffer.
     ``stats`` ("sum" / "summax"): the same pass emits the output's per-plane partial statistics for a following
@@ -271,6 +291,8 @@ def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, 
     (S1_NECK), "backbone" for the backbone's (S1_BACKBONE).
     ``n1``: one of the wide 1x1 convs (the fp16-split 1x1 kernel, with out / out2): True for the neck's (N1_NECK),
     "backbone" for the backbone's (N1_BACKBONE, which may name layers: ``layer`` is the index of the conv's layer).
+    ``stats_layer``: the layer index of a neck n1 conv that feeds a gate (Conv.n1_stats_layer): with ``stats`` it takes
+    the n1 route only where N1_STATS selects that layer.
     Returns None when the fast path does not apply (CPU tensor, no bias, unsupported activation / shape)."""
     if x.device.type != "cuda" or conv.bias is None or act_code is None or x.dtype not in (torch.float32,
                                                                                            torch.bfloat16):
@@ -291,10 +313,12 @@ def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, 
             and (CONV3X3 == "all" or tower) and _hip.conv3x3_ok(x, conv)):
         prep = lambda: _cached(conv, "c3prep", (conv.weight,), lambda: _hip.conv3x3_prepare(conv.weight))  # noqa: E731
         return _hip.conv3x3_silu(x, conv.bias, prep, conv.out_channels)
-    if (split and _n1_on(n1, layer) and act_code == 1 and res is None and stats is None
+    if (split and _n1_on(n1, layer) and act_code == 1 and res is None
+            and (stats is None or (n1 is True and out2 is None and stats in ("sum", "summax", "capool")
+                                   and _n1_stats_on(stats_layer)))
             and _hip.conv1x1x2_ok(x, conv) and (out is None or _hip._imgs_contig(out))
             and (out2 is None or _hip._imgs_contig(out2))):
-        return _n1_run(conv, x, out, out2, c2lo, n1)
+        return _n1_run(conv, x, out, out2, c2lo, n1, stats)
     if (split and _s1_on(s1) and act_code == 1 and stats is None and out2 is None and _hip.conv3x3_ok(x, conv)
             and x.shape[3] % 4 == 0 and (res is None or _hip._imgs_contig(res))):
         prep = lambda: _cached(conv, "c3prep", (conv.weight,), lambda: _hip.conv3x3_prepare(conv.weight))  # noqa: E731
@@ -371,6 +395,9 @@ class Conv(nn.Module):
     # the index in DetectionModel.model of the C2f / SPPF an n1_backbone conv belongs to, handed to conv_epilogue as
     # its ``layer`` (``layer`` itself stays the stride-2 convs': a conv carries at most one of the two marks)
     n1_layer = None
+    # set by DetectionModel on a neck n1 conv whose output feeds an SE / CBAM / CA directly (emit_stats): the index of
+    # its layer, which N1_STATS may name; such a conv takes the n1 route only with its statistics (conv_epilogue)
+    n1_stats_layer = None
     # set by DetectionModel on layer 0 when it is a 3-channel 3x3 / stride-2 Conv feeding an SE: the stem kernel (STEM_HIP)
     stem = False
 
@@ -402,7 +429,7 @@ class Conv(nn.Module):
         y = conv_epilogue(self.conv, _act_code(self.act), x, out, res, self.emit_stats, out2, c2lo, self.tower,
                           "backbone" if self.s2_backbone else self.s2, self.s1_mark(),
                           "backbone" if self.n1_backbone else self.n1,
-                          self.n1_layer if self.n1_backbone else self.layer)
+                          self.n1_layer if self.n1_backbone else self.layer, self.n1_stats_layer)
         if y is not None:
             return y
         if isinstance(x, _hip.CatView):

@@ -494,6 +494,8 @@ class DetectionModel(BaseModel):
                            [m.cv1, m.cv2] if isinstance(m, M.C2f) else []):
                     if cv.conv.kernel_size == (1, 1) and cv.conv.groups == 1 and cv.conv.out_channels % 128 == 0:
                         cv.n1 = True
+                        if cv.emit_stats is not None:  # feeds a gate: the kernel's statistics forms (modules.N1_STATS)
+                            cv.n1_stats_layer = i
             # the backbone's wide 1x1 convs (modules.N1_BACKBONE, which may name layers): cv1 / cv2 of C2f and SPPF
             elif isinstance(m, (M.C2f, M.SPPF)):
                 for cv in (m.cv1, m.cv2):

@@ -174,6 +174,12 @@ def producer_of(key):
         cout = extra[0]
         plain = ("conv1x1_thin", tuple(shape), (cout, False, False)) + tail
         return PRODUCER_GATE[extra[1]], (B, cout, H, W), plain, B * H * W * (cin + cout) * E
+    if op == "conv1x1x2_stats" and isinstance(extra, tuple) and len(extra) == 2 and extra[1] in PRODUCER_GATE:
+        # the fp16-split 1x1 kernel's statistics forms (csrc/conv1x1x2.hip; "capool": its plain launch before a CA)
+        B, cin, H, W = shape
+        cout = extra[0]
+        plain = ("conv1x1x2", tuple(shape), (cout, False)) + tail
+        return PRODUCER_GATE[extra[1]], (B, cout, H, W), plain, B * H * W * (cin + cout) * E
     if op == "stem" and isinstance(extra, tuple) and len(extra) == 2 and extra[1] in PRODUCER_GATE:
         # the stem kernel (csrc/stem.hip) has no plain variant in the model: its plain pass is priced at the HBM roof of
         # its own bytes (the image batch read once + the stride-2 map written once)
