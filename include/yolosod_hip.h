@@ -435,9 +435,6 @@ int yolosod_debug_set_conv1x1x2_form(int form);
 /* The form (same encoding, no field 0) a [B][*][H][W] -> cout launch of yolosod_conv1x1x2_silu* runs in under the
  * current setting; 0 for shapes the kernel does not take (H * W not a multiple of 4, unsupported cout). */
 int yolosod_debug_conv1x1x2_form(int B, int cout, int H, int W);
-/* Timing hook: ablation variants of the stride-2 conv kernel at Cout 64 with a channel gate (csrc/conv3x3s2.hip; WRONG
- * results for abl != 0 - scripts/bench_conv3x3s2.py only). Returns the previous value. */
-int yolosod_debug_set_conv3x3s2_abl(int abl);
 /* Test / measurement hook: the form the tiled stride-2 conv kernel (csrc/conv3x3s2.hip) takes. form = geometry +
  * 4 * groups: geometry 0 automatic, 1 the 32 x 2 output tile of 16 x 1 pixel blocks, 2 the 40 x 2 tile of 8 x 2 blocks,
  * 3 the 20 x 4 tile of 4 x 4 blocks; groups 0 automatic, 1 128-channel output groups, 2 64-channel groups (Cout 64 always
@@ -447,9 +444,6 @@ int yolosod_debug_set_conv3x3s2_form(int form);
 /* The form (same encoding, no field 0) a [B][*][H][W] -> cout launch of yolosod_conv3x3s2_silu* runs in under the
  * current setting; 0 for shapes the kernel does not take (output width not a multiple of 4, unsupported cout). */
 int yolosod_debug_conv3x3s2_form(int B, int cout, int H, int W);
-/* Timing hook: ablation variants of the 3x3 conv kernel (csrc/conv3x3.hip; WRONG results for any abl != 0 and
- * != 16 - scripts/bench_conv3x3.py only). Returns the previous value. */
-int yolosod_debug_set_conv3x3_abl(int abl);
 /* Test / measurement hook: force the form of the persistent 3x3 conv kernel (csrc/conv3x3.hip, W % 4 == 0 shapes);
  * every form gives bit-identical results. form = geometry + 4 * groups. geometry: 0 automatic (the fewest tiles for
  * the map), 1 the 32 x 8 tile of 16 x 1 blocks, 2 the 20 x 12 tile of 4 x 4 blocks, 3 the 40 x 6 tile of 8 x 2

@@ -1,7 +1,7 @@
 """Micro-benchmark: the stride-1 3x3 convs of the n640 step (bs 32) - the Detect towers and the backbone's / neck's C2f
 Bottleneck convs (Cout 32 .. 256, with and without the shortcut) - on the fp16-split kernel vs MIOpen (F.conv2d without
 bias + the HIP bias / SiLU (+ shortcut) epilogue, as the executor runs it). GPU only.
-python scripts/bench_conv3x3.py [forms | bottleneck [H [batches]] | <abl>,...]; YOLOSOD_LIB_AB=<lib> times another build of the library."""
+python scripts/bench_conv3x3.py [forms | bottleneck [H [batches]]]; YOLOSOD_LIB_AB=<lib> times another build of the library."""
 import sys
 from pathlib import Path
 
@@ -30,27 +30,6 @@ def timed(fn, reps=50):
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / reps
 
-
-ABL = [int(a) for a in sys.argv[1].split(",")] if len(sys.argv) > 1 and sys.argv[1] not in ("forms", "bottleneck") else []
-if ABL:  # timing ablations of the kernel (wrong results): see yolosod_debug_set_conv3x3_abl
-    lib = _hip.load_library()
-    for shape in SHAPES[:2]:
-        B, cin, H, W = shape
-        x = torch.randn(shape, device=dev)
-        w = torch.randn(64, cin, 3, 3, device=dev) * 0.05
-        b = torch.randn(64, device=dev) * 0.1
-        prep = _hip.conv3x3_prepare(w)
-        gf = 2 * B * H * W * 64 * cin * 9 / 1e9
-        lib.yolosod_debug_set_conv3x3_abl(0)
-        y0 = _hip.conv3x3_silu(x, b, lambda: prep)
-        for a in ABL:
-            lib.yolosod_debug_set_conv3x3_abl(a)
-            t_k = timed(lambda: _hip.conv3x3_silu(x, b, lambda: prep))
-            d = (_hip.conv3x3_silu(x, b, lambda: prep) - y0).abs().max().item()  # 0 for the exact variants
-            print(f"{str(shape):22s} abl {a:2d} {t_k:7.3f} ms ({gf / t_k:6.1f} TF/s)  max|y - y_abl0| {d:.3g}",
-                  flush=True)
-        lib.yolosod_debug_set_conv3x3_abl(0)
-    sys.exit(0)
 
 if len(sys.argv) > 1 and sys.argv[1] == "bottleneck":
     # the 32-channel Bottleneck (32 -> 32 -> 32 with the shortcut) in place in a C2f's 96-channel buffer, input

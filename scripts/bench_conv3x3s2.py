@@ -1,6 +1,6 @@
 """Micro-benchmark: the gate-consumer stride-2 convs at the n640 / m640 shapes on the fused kernel (gate applied at
 staging) vs what it replaces: the gate's apply pass + MIOpen conv (no bias) + the HIP bias / SiLU epilogue. GPU only.
-python scripts/bench_conv3x3s2.py [forms | <abl>,...]; "forms" times every form of the tiled kernel on the stride-2
+python scripts/bench_conv3x3s2.py [forms]; "forms" times every form of the tiled kernel on the stride-2
 launch shapes of the n640 step; YOLOSOD_LIB_AB=<lib> times another build of the library (one form if it predates the
 hook)."""
 import sys
@@ -72,22 +72,6 @@ if FORMS_MODE:
         if has:
             lib.yolosod_debug_set_conv3x3s2_form(0)
         print(line, flush=True)
-    sys.exit(0)
-
-ABL = [int(a) for a in sys.argv[1].split(",")] if len(sys.argv) > 1 else []
-if ABL:  # timing ablations at the SE L1 -> L2 shape (wrong results): yolosod_debug_set_conv3x3s2_abl
-    lib = _hip.load_library()
-    (B, cin, H, W), cout, _ = SHAPES[0]
-    x = torch.randn(B, cin, H, W, device=dev)
-    w = torch.randn(cout, cin, 3, 3, device=dev) * 0.05
-    b = torch.randn(cout, device=dev) * 0.1
-    gc = torch.sigmoid(torch.randn(B, cin, device=dev))
-    prep = _hip.conv3x3s2_prepare(w)
-    for a in ABL:
-        lib.yolosod_debug_set_conv3x3s2_abl(a)
-        t = timed(lambda: _hip.conv3x3s2_silu(x, b, lambda: prep, cout, gc))
-        print(f"abl {a:2d} {t:7.3f} ms", flush=True)
-    lib.yolosod_debug_set_conv3x3s2_abl(0)
     sys.exit(0)
 
 for shape, cout, gates in SHAPES:

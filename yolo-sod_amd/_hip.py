@@ -107,7 +107,6 @@ SIGNATURES = {
     "yolosod_init": (_i, [_i]),
     "yolosod_debug_set_a2_fused": (_i, [_i]),
     "yolosod_debug_set_a2_pool_wide": (_i, [_i]),
-    "yolosod_debug_set_conv3x3_abl": (_i, [_i]),
     "yolosod_debug_set_conv3x3_form": (_i, [_i]),
     "yolosod_debug_conv3x3_form": (_i, [_i, _i, _i, _i]),
     "yolosod_debug_conv3x3_form_ex": (_i, [_i, _i, _i, _i, _i]),
@@ -116,7 +115,6 @@ SIGNATURES = {
     "yolosod_debug_set_bottleneck3x3_fuse": (_i, [_i]),
     "yolosod_debug_set_conv1x1x2_form": (_i, [_i]),
     "yolosod_debug_conv1x1x2_form": (_i, [_i, _i, _i, _i]),
-    "yolosod_debug_set_conv3x3s2_abl": (_i, [_i]),
     "yolosod_debug_set_conv3x3s2_form": (_i, [_i]),
     "yolosod_debug_conv3x3s2_form": (_i, [_i, _i, _i, _i]),
     "yolosod_se_gate": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
@@ -866,18 +864,24 @@ def conv3x3_ok(x, conv) -> bool:
             and int(load_library().yolosod_conv3x3_prep_bytes_ex(int(conv.in_channels), int(conv.out_channels))) > 0)
 
 
+def _split_prepare(name, bytes_fn, prepare_fn, w):
+    """Prepared block (uint8 tensor) of the conv weight ``w`` [Cout, Cin, ...] for the fp16-split conv kernel ``name``
+    (csrc/split_conv.h); ``bytes_fn`` / ``prepare_fn``: the kernel's yolosod_*_prep_bytes / *_prepare entries."""
+    cout, cin = int(w.shape[0]), int(w.shape[1])
+    nbytes = int(bytes_fn(cin, cout))
+    if nbytes == 0:
+        raise RuntimeError(f"{name}: (Cin={cin}, Cout={cout}) unsupported")
+    blk = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    wc = w.detach().float().contiguous()
+    _check(_launch((f"{name}_prep", (cout, cin), None), w.device, prepare_fn, _dev(wc, "weight"), cin, cout,
+                   blk.data_ptr(), nbytes, _stream(w.device)), f"{name}_prepare")
+    return blk
+
+
 def conv3x3_prepare(w):
     """Prepared block (fragment-major fp16 split planes of 64 W, uint8 tensor) of a [Cout, Cin, 3, 3] fp32 weight."""
     lib = load_library()
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    nbytes = int(lib.yolosod_conv3x3_prep_bytes_ex(cin, cout))
-    if nbytes == 0:
-        raise RuntimeError(f"conv3x3: (Cin={cin}, Cout={cout}) unsupported")
-    blk = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-    wc = w.detach().float().contiguous()
-    _check(_launch(("conv3x3_prep", (cout, cin), None), w.device, lib.yolosod_conv3x3_prepare_ex, _dev(wc, "weight"),
-                   cin, cout, blk.data_ptr(), nbytes, _stream(w.device)), "conv3x3_prepare")
-    return blk
+    return _split_prepare("conv3x3", lib.yolosod_conv3x3_prep_bytes_ex, lib.yolosod_conv3x3_prepare_ex, w)
 
 
 def _img_view(t, shape, name):
@@ -1019,15 +1023,8 @@ def conv1x1x2_ok(x, conv) -> bool:
 def conv1x1x2_prepare(w):
     """Prepared block (fragment-major fp16 split planes of 64 W, Cin padded to 128) of a [Cout, Cin(, 1, 1)] weight."""
     lib = load_library()
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    nbytes = int(lib.yolosod_conv1x1x2_prep_bytes(cin, cout))
-    if nbytes == 0:
-        raise RuntimeError(f"conv1x1x2: (Cin={cin}, Cout={cout}) unsupported")
-    blk = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-    wc = w.detach().float().reshape(cout, cin).contiguous()
-    _check(_launch(("conv1x1x2_prep", (cout, cin), None), w.device, lib.yolosod_conv1x1x2_prepare, _dev(wc, "weight"),
-                   cin, cout, blk.data_ptr(), nbytes, _stream(w.device)), "conv1x1x2_prepare")
-    return blk
+    return _split_prepare("conv1x1x2", lib.yolosod_conv1x1x2_prep_bytes, lib.yolosod_conv1x1x2_prepare,
+                          w.reshape(int(w.shape[0]), int(w.shape[1])))
 
 
 def conv1x1x2_silu(x, bias, prep, cout, out=None, out2=None, c2lo=0, op="conv1x1x2", stats=None):
@@ -1103,15 +1100,7 @@ def conv3x3s2_ok(x, conv) -> bool:
 def conv3x3s2_prepare(w):
     """Prepared block (fragment-major fp16 split planes of 64 W, uint8 tensor) of a [Cout, Cin, 3, 3] fp32 weight."""
     lib = load_library()
-    cout, cin = int(w.shape[0]), int(w.shape[1])
-    nbytes = int(lib.yolosod_conv3x3s2_prep_bytes(cin, cout))
-    if nbytes == 0:
-        raise RuntimeError(f"conv3x3s2: (Cin={cin}, Cout={cout}) unsupported")
-    blk = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-    wc = w.detach().float().contiguous()
-    _check(_launch(("conv3x3s2_prep", (cout, cin), None), w.device, lib.yolosod_conv3x3s2_prepare, _dev(wc, "weight"),
-                   cin, cout, blk.data_ptr(), nbytes, _stream(w.device)), "conv3x3s2_prepare")
-    return blk
+    return _split_prepare("conv3x3s2", lib.yolosod_conv3x3s2_prep_bytes, lib.yolosod_conv3x3s2_prepare, w)
 
 
 def conv3x3s2_silu(x, bias, prep, cout, gate_c=None, gate_p=None, key=None, out=None):

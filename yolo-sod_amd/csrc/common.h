@@ -277,6 +277,8 @@ __device__ __forceinline__ void range_report(unsigned* flag, float m) {
 }
 // host: the device's flag word (allocated and zeroed on first use, one per device)
 unsigned* range_flag_dev();
+// host (runtime.hip): the device's compute units, read once (256 if the query fails)
+int cu_count();
 
 // c += A.B for split operands (A = (ah, al), B = (bh, bl)), smallest terms first
 __device__ __forceinline__ f32x4 mfma_f16x3(f16x8_t ah, f16x8_t al, f16x8_t bh, f16x8_t bl, f32x4 c) {

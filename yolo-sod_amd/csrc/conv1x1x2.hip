@@ -25,12 +25,12 @@
 // registers the epilogue holds; thin_stats_reduce_kernel (conv_epilogue.hip) adds a plane's tiles in a fixed order
 // into the PlaneStats layout the gates read. No atomics: deterministic and independent of the batch size. Everything
 // up to the store is the STATS 0 code, so the stored output is bit-identical to it.
-#include "common.h"
+#include "split_conv.h"
 
 namespace ys {
 namespace c1 {
 
-constexpr float WSC = 64.0f;
+constexpr float WSC = SPLIT_WSC;
 constexpr int KS = 128;        // input channels per stage
 constexpr int PS = KS + 8;     // plane row stride (halves): 272-byte pixel rows
 constexpr int NT = 256;
@@ -61,32 +61,13 @@ struct Args {
 #include "conv1x1x2_kernel.h"
 #undef YS_C1_STATS_FORMS
 
-// W [Cout][Cin] -> fragment-major planes of 64 W: one thread per (output channel, input channel)
-__global__ __launch_bounds__(256) void conv1x1_prep_kernel(const float* __restrict__ w, int cin, int cin_pad,
-                                                           int cout, h16_t* __restrict__ wp, unsigned* range_flag,
-                                                           unsigned* prep_flag) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long)cout * cin_pad) return;
-  const int k = (int)(i % cin_pad), n = (int)(i / cin_pad);
-  const float v = k < cin ? w[(long)n * cin + k] * WSC : 0.f;  // zero weights for the padded channels
-  const _Float16 hh = (_Float16)v;
-  const _Float16 ll = (_Float16)(v - (float)hh);
-  const int s = k >> 5, kk = k & 31, cbk = n >> 4, ncb = cout >> 4;
-  const int ln = ((kk >> 3) << 4) + (n & 15);
-  const long base = ((long)(s * ncb + cbk) * 2) * 512 + ln * 8 + (kk & 7);
-  wp[base] = __builtin_bit_cast(h16_t, hh);
-  wp[base + 512] = __builtin_bit_cast(h16_t, ll);
-  const float m = fabsf(v);
-  range_report(range_flag, m);
-  range_report(prep_flag, m);
-}
-
 }  // namespace c1
 }  // namespace ys
 
 using namespace ys;
 
 static int c1_pad(int cin) { return (cin + c1::KS - 1) / c1::KS * c1::KS; }
+static size_t c1_halves(int cin, int cout) { return (size_t)2 * cout * c1_pad(cin); }  // of the prepared planes
 
 // Forced form of the kernel (tests / per-shape measurements compare forms; the automatic choice is the product):
 // form = groups + 4 buffers; groups 0 automatic, 1 workgroups of 128 output channels, 2 of 256 (Cout % 256 == 0; any
@@ -99,18 +80,6 @@ YS_EXPORT int yolosod_debug_set_conv1x1x2_form(int form) {
   return old;
 }
 
-static int c1_cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, c = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0)
-      c = 256;
-    n = c;
-  }
-  return n;
-}
-
 // The resolved form (groups 1 .. 2 + 4 * buffers 1 .. 2) of a launch: the forced fields of g_c1_form, the automatic
 // choice for the others. Automatic (scripts/bench_conv1x1x2.py forms, batch 32, each library twice):
 // 256-channel groups for Cout 512 on maps of at most 20 x 20 when the 128-channel items would not fit the workgroup
@@ -121,7 +90,7 @@ static int c1_form(int B, int cout, int HW) {
   if (cout == 64) return 1 + 4 * 1;
   const int fgrp = g_c1_form & 3, fbuf = g_c1_form >> 2;
   const bool g256 = fgrp ? fgrp == 2
-                         : cout == 512 && HW <= 400 && (long)B * ((HW + 63) / 64) * (cout / 128) > 2L * c1_cu_count();
+                         : cout == 512 && HW <= 400 && (long)B * ((HW + 63) / 64) * (cout / 128) > 2L * cu_count();
   return (g256 && cout % 256 == 0 ? 2 : 1) + 4 * (fbuf ? fbuf : 1);
 }
 
@@ -143,39 +112,15 @@ static void c1_launch(bool dual, unsigned nwg, hipStream_t st, const c1::Args& a
 // Cout 64 or a multiple of 128 (<= 1024), Cin a multiple of 32 (<= 4096; the weights are padded to a multiple of 128)
 YS_EXPORT size_t yolosod_conv1x1x2_prep_bytes(int cin, int cout) {
   if (cin <= 0 || cin % 32 || cin > 4096 || cout <= 0 || (cout != 64 && cout % 128) || cout > 1024) return 0;
-  Sizer s;
-  s.take<h16_t>((size_t)2 * cout * c1_pad(cin));
-  s.take<unsigned>(1);
-  return s.off;
-}
-
-static bool c1_carve(void* buf, size_t bytes, int cin, int cout, h16_t** wp, unsigned** flag) {
-  Carver cv(buf, bytes);
-  *wp = cv.take<h16_t>((size_t)2 * cout * c1_pad(cin));
-  *flag = cv.take<unsigned>(1);
-  return *flag != nullptr;
+  return split_prep_bytes(c1_halves(cin, cout));
 }
 
 // Weight preparation (re-run whenever the weights change): w [cout][cin] fp32 (BN folded) -> prep block.
 YS_EXPORT int yolosod_conv1x1x2_prepare(const float* w, int cin, int cout, void* prep, size_t prep_bytes,
                                         void* stream) {
-  YS_CHECK_ARG(w && prep, "conv1x1x2_prepare: null pointer");
   YS_CHECK_ARG(yolosod_conv1x1x2_prep_bytes(cin, cout) > 0, "conv1x1x2_prepare: (cin=%d, cout=%d) unsupported", cin,
                cout);
-  h16_t* wp;
-  unsigned* flag;
-  YS_CHECK_ARG(c1_carve(prep, prep_bytes, cin, cout, &wp, &flag), "conv1x1x2_prepare: block too small (%zu)",
-               prep_bytes);
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(flag, 0, sizeof(unsigned), st) != hipSuccess) {
-    set_error("conv1x1x2_prepare: flag reset failed");
-    return -1;
-  }
-  const long n = (long)cout * c1_pad(cin);
-  hipLaunchKernelGGL(c1::conv1x1_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, cin, c1_pad(cin),
-                     cout, wp, range_flag_dev(), flag);
-  YS_CHECK_LAUNCH("conv1x1x2_prep");
-  return 0;
+  return split_prepare<1>("conv1x1x2_prepare", w, cin, c1_pad(cin), cout, prep, prep_bytes, stream);
 }
 
 // y = SiLU(W [x; x2] + bias): x image b at x + b x_bstride ([k1][HW]), x2 (or NULL) image b at x2 + b x2_bstride
@@ -203,14 +148,13 @@ YS_EXPORT int yolosod_conv1x1x2_silu_cat(const float* x, long x_bstride, const f
   YS_CHECK_ARG(!y2 || (c2lo >= 0 && c2lo < cout && y2_bstride >= (long)(cout - c2lo) * HW), "conv1x1x2: c2lo=%d",
                c2lo);
   if (B == 0) return 0;
-  h16_t* wp;
-  unsigned* flag;
-  YS_CHECK_ARG(c1_carve(const_cast<void*>(prep), prep_bytes, cin, cout, &wp, &flag),
+  SplitPrep sp;
+  YS_CHECK_ARG(split_prep_carve(prep, prep_bytes, c1_halves(cin, cout), &sp),
                "conv1x1x2: prepared block too small");
   constexpr int NPx = 64;  // pixels per tile (128-pixel tiles measured slower on four of five neck shapes)
   const int ntile = (HW + NPx - 1) / NPx;
-  c1::Args a{x, x_bstride, wp, bias, y, y_bstride, y2, y2_bstride, c2lo, cin, cout, HW, ntile, range_flag_dev(), flag,
-             x2, x2_bstride, k1, up_w};
+  c1::Args a{x, x_bstride, sp.wp, bias, y, y_bstride, y2, y2_bstride, c2lo, cin, cout, HW, ntile, range_flag_dev(),
+             sp.flag, x2, x2_bstride, k1, up_w};
   const int form = c1_form(B, cout, HW);
   const bool g256 = (form & 3) == 2, db = (form >> 2) == 2;
   const long nwg = (long)B * ntile * (cout == 64 ? 1 : cout / (g256 ? 256 : 128));
@@ -260,15 +204,14 @@ YS_EXPORT int yolosod_conv1x1x2_silu_stats(const float* x, long x_bstride, float
   YS_CHECK_ARG((long)c1_pad(cin) * HW * 4 < (1L << 32), "conv1x1x2_stats: image too large for 32-bit buffer offsets");
   YS_CHECK_ARG(((uintptr_t)y & 15) == 0 && y_bstride % 4 == 0, "conv1x1x2_stats: output must be 16-byte aligned");
   if (B == 0) return 0;
-  h16_t* wp;
-  unsigned* flag;
-  YS_CHECK_ARG(c1_carve(const_cast<void*>(prep), prep_bytes, cin, cout, &wp, &flag),
+  SplitPrep sp;
+  YS_CHECK_ARG(split_prep_carve(prep, prep_bytes, c1_halves(cin, cout), &sp),
                "conv1x1x2_stats: prepared block too small");
   const int ntile = (HW + 63) / 64;
   float* tsum = tile_ws;
   float* tmax = tile_ws + (long)B * cout * ntile;
-  c1::Args a{x, x_bstride, wp, bias, y, y_bstride, tsum, tmax - tsum, 0, cin, cout, HW, ntile, range_flag_dev(), flag,
-             nullptr, 0, cin, 0};
+  c1::Args a{x, x_bstride, sp.wp, bias, y, y_bstride, tsum, tmax - tsum, 0, cin, cout, HW, ntile, range_flag_dev(),
+             sp.flag, nullptr, 0, cin, 0};
   const bool g256 = (c1_form(B, cout, HW) & 3) == 2;
   const long nwg = (long)B * ntile * (cout / (g256 ? 256 : 128));
   YS_CHECK_ARG(nwg < (1L << 31), "conv1x1x2_stats: too many tiles");

@@ -6,9 +6,9 @@
 //
 // Method (the two-term split of swin_x3.hip): v = h + l with h = fp16(v), l = fp16(v - h); a product is
 // ah.bh + ah.bl + al.bh on v_mfma_f32_16x16x32_f16 with fp32 accumulation. Weights are split once per parameter
-// version by conv3x3_prep_kernel (x 64, exact, so their low terms stay normal fp16) into fragment-major planes:
-// for tap t, 32-channel input chunk q, 16-channel output block rb and plane p, the 64 lanes' fragments (lane (g, l15):
-// output channel 16 rb + l15, input channels 32 q + 8 g .. + 7) are 1 KB contiguous.
+// version by split_prep_kernel (split_conv.h; x 64, exact, so their low terms stay normal fp16) into fragment-major
+// planes: for tap t, 32-channel input chunk q, 16-channel output block rb and plane p, the 64 lanes' fragments (lane
+// (g, l15): output channel 16 rb + l15, input channels 32 q + 8 g .. + 7) are 1 KB contiguous.
 //
 // One 256-thread workgroup per (image, 8 x 32 output tile), all 64 output channels, two workgroups per CU: per input
 // chunk, the tile's 10 x 34 input halo (zero padding outside the image) is loaded, split and stored once as two fp16
@@ -18,12 +18,12 @@
 // blocks 2 (w & 1), 2 (w & 1) + 1: 16 accumulator tiles from 4 weight fragments (L2, one tap ahead) and 16 pixel
 // fragments (LDS) per tap. The pixels are the MFMA's A operand, so a lane's accumulators are 4 consecutive pixels of
 // one channel (16-byte stores). The next chunk's halo loads are spread over the current chunk's taps.
-#include "common.h"
+#include "split_conv.h"
 
 namespace ys {
 namespace c3 {
 
-constexpr float WSC = 64.0f;
+constexpr float WSC = SPLIT_WSC;
 constexpr int TH = 8, TW = 32;              // output tile
 constexpr int HH = TH + 2, HW_ = TW + 2;    // halo tile
 constexpr int NPXH = HH * HW_;              // 340 halo pixels
@@ -49,11 +49,10 @@ struct Args {
   long xbs;            // image b of x at x + b xbs (>= cin H W: x may be a channel slice of a concat buffer)
 };
 
-// ABL (timing ablations, wrong results; yolosod_debug_set_conv3x3_abl): 1 no halo loads, 2 every weight fragment from
-// one address, 4 no MFMA (a VALU stand-in keeps the LDS reads), 8 no output stores. V4: W % 4 == 0 (16-byte stores).
+// One tile per workgroup (the shapes the persistent form below does not take). V4: W % 4 == 0 (16-byte stores).
 // CBW: 16-channel blocks per wave (2: output groups of 64 channels; 1: of 32, the neck's C2f at P2), the workgroup's
 // group = blockIdx % groups (the groups of a tile run side by side and share its input in L2). RES: + residual.
-template <int ABL, bool V4, int CBW = 2, bool RES = false>
+template <bool V4, int CBW = 2, bool RES = false>
 __global__ __launch_bounds__(256, 2) void conv3x3_x2_kernel(Args p) {
   __shared__ __attribute__((aligned(16))) h16_t Pl[2 * PL];
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -101,13 +100,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_x2_kernel(Args p) {
     const __amdgpu_buffer_rsrc_t r = live ? rx : rx0;
 #pragma unroll
     for (int k = 0; k < 4 * NIT; ++k)
-      if (k >= k0 && k < k1) {
-        if constexpr ((ABL & 1) != 0)
-          sv[k >> 2][k & 3] = 0.5f + (float)q;
-        else
-          sv[k >> 2][k & 3] = __builtin_bit_cast(
-              float, __builtin_amdgcn_raw_buffer_load_b32(r, voff[k >> 2], sx + (k & 3) * HWi * 4, 0));
-      }
+      if (k >= k0 && k < k1)
+        sv[k >> 2][k & 3] = __builtin_bit_cast(
+            float, __builtin_amdgcn_raw_buffer_load_b32(r, voff[k >> 2], sx + (k & 3) * HWi * 4, 0));
   };
   auto store_chunk = [&]() __attribute__((always_inline)) {
 #pragma unroll
@@ -137,7 +132,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_x2_kernel(Args p) {
   // q start at byte ((t nq + q) ncb_all 2) KB, [channel block][plane][lane][16 bytes] (B-operand lane layout = A's)
   const int cbw0 = grp * 2 * CBW + CBW * rp;
   auto wfrag = [&](int t, int q, int r, int pl) __attribute__((always_inline)) {
-    const int st = (ABL & 2) ? 0 : __builtin_amdgcn_readfirstlane(((t * nq + q) * p.ncb_all * 2) * 1024);
+    const int st = __builtin_amdgcn_readfirstlane(((t * nq + q) * p.ncb_all * 2) * 1024);
     return __builtin_bit_cast(f16x8_t, __builtin_amdgcn_raw_buffer_load_b128(
                                            rw, (unsigned)((((cbw0 + r) * 2 + pl) * 64 + lane) * 16), st, 0));
   };
@@ -185,13 +180,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_x2_kernel(Args p) {
         const f16x8_t xlo = *reinterpret_cast<const f16x8_t*>(src + PL);
 #pragma unroll
         for (int r = 0; r < CBW; ++r) {
-          if constexpr ((ABL & 4) != 0) {
-            acc[r][cb][0] += (float)xh[0] * (float)wa[r][0][0] + (float)xlo[1] * (float)wa[r][1][1];
-          } else {  // the three split products, small terms first
-            f32x4 c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wa[r][1], acc[r][cb], 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xlo, wa[r][0], c, 0, 0, 0);
-            acc[r][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wa[r][0], c, 0, 0, 0);
-          }
+          // the three split products, small terms first
+          f32x4 c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wa[r][1], acc[r][cb], 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_16x16x32_f16(xlo, wa[r][0], c, 0, 0, 0);
+          acc[r][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(xh, wa[r][0], c, 0, 0, 0);
         }
       }
 #pragma unroll
@@ -211,8 +203,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_x2_kernel(Args p) {
 #pragma unroll
   for (int cb = 0; cb < 8; ++cb) {
     const int oy = ty * TH + 4 * ph + (cb >> 1), ox = tx * TW + (cb & 1) * 16 + 4 * g;
-    if constexpr ((ABL & 8) != 0)
-      if (acc[0][cb][0] != -1.2345e30f) continue;
 #pragma unroll
     for (int r = 0; r < CBW; ++r) {
       const long po = (long)(16 * (cbw0 + r) + l15) * HWi + oy * W + ox;
@@ -890,39 +880,10 @@ __global__ __launch_bounds__(BN_NT) void bottleneck3x3_c32_kernel(BnArgs p) {
     *p.range_flag = 1u;
 }
 
-// W [64][Cin][3][3] -> fragment-major planes of 64 W (see the file comment); one thread per (output channel, input
-// channel, tap). The block's own range word records whether 64 W left fp16's range (re-reported by every launch).
-__global__ __launch_bounds__(256) void conv3x3_prep_kernel(const float* __restrict__ w, int cin, int cout,
-                                                           h16_t* __restrict__ wp, unsigned* range_flag,
-                                                           unsigned* prep_flag) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  const long n_all = (long)cout * cin * 9;
-  if (i >= n_all) return;
-  const int t = (int)(i % 9), k = (int)((i / 9) % cin), n = (int)(i / (9L * cin));
-  const float v = w[i] * WSC;
-  const _Float16 hh = (_Float16)v;
-  const _Float16 ll = (_Float16)(v - (float)hh);
-  const int nq = cin >> 5, q = k >> 5, kk = k & 31, rb = n >> 4, ncb = cout >> 4;
-  const int ln = ((kk >> 3) << 4) + (n & 15);
-  const long base = ((long)((t * nq + q) * ncb + rb) * 2) * 512 + ln * 8 + (kk & 7);
-  wp[base] = __builtin_bit_cast(h16_t, hh);
-  wp[base + 512] = __builtin_bit_cast(h16_t, ll);
-  const float m = fabsf(v);
-  range_report(range_flag, m);
-  range_report(prep_flag, m);
-}
-
 }  // namespace c3
 }  // namespace ys
 
 using namespace ys;
-
-static int g_c3_abl = 0;
-YS_EXPORT int yolosod_debug_set_conv3x3_abl(int abl) {
-  const int old = g_c3_abl;
-  g_c3_abl = abl;
-  return old;
-}
 
 // Forced form of the persistent kernel (tests / per-shape measurements compare forms; the automatic choice is the
 // product): form = geometry + 4 groups; geometry 0 automatic, 1 the 32 x 8 tile, 2 the 20 x 12 tile of 4 x 4 blocks,
@@ -943,26 +904,8 @@ static const int C3_GEO_TH[3] = {c3::GeoD<0>::TH, c3::GeoD<1>::TH, c3::GeoD<2>::
 // The geometry with the fewest tiles (every tile is 16 block slots of MFMA work, useful or not) for an H x W map; the
 // 32 x 8 tile on a tie and for every map above 40 x 40 (P2 / P3: the form those shapes were tuned on).
 static int c3_pick_geo(int H, int W) {
-  if ((long)H * W > 1600) return 0;
-  int best = 0;
-  long nbest = 0;
-  for (int g = 0; g < 3; ++g) {
-    const long n = (long)((W + C3_GEO_TW[g] - 1) / C3_GEO_TW[g]) * ((H + C3_GEO_TH[g] - 1) / C3_GEO_TH[g]);
-    if (g == 0 || n < nbest) best = g, nbest = n;
-  }
-  return best;
-}
-
-static int c3_cu_count() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, c = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0)
-      c = 256;
-    n = c;
-  }
-  return n;
+  static const int slots[3] = {16, 16, 16};
+  return pick_geo(H, W, C3_GEO_TW, C3_GEO_TH, slots);
 }
 
 // The resolved form (geometry 1 .. 3 + 4 * groups 1 .. 2) of a W % 4 == 0 launch: the forced fields of g_c3_form, the
@@ -981,7 +924,7 @@ static int c3_form(int B, int cin, int cout, int H, int W) {
     const int grp = fgrp == 3 ? (cin == 32 ? 3 : 2) : fgrp == 4 ? 4 : fgrp == 0 && cin == 32 ? C3_AUTO_C32[geo] : 2;
     return geo + 1 + 4 * grp;
   }
-  const bool g32 = fgrp ? fgrp >= 2 : ntiles * (cout / 64) < 2L * c3_cu_count();
+  const bool g32 = fgrp ? fgrp >= 2 : ntiles * (cout / 64) < 2L * cu_count();
   return geo + 1 + 4 * (g32 ? 2 : 1);
 }
 
@@ -990,10 +933,7 @@ static bool c3_cout_ok(int cout) { return cout == 32 || (cout % 64 == 0 && cout 
 // 3x3 / stride 1 / pad 1 conv with Cout 32 or a multiple of 64 (<= 512): Cin a multiple of 32 (<= 2048)
 YS_EXPORT size_t yolosod_conv3x3_prep_bytes_ex(int cin, int cout) {
   if (cin <= 0 || cin % 32 || cin > 2048 || !c3_cout_ok(cout)) return 0;
-  Sizer s;
-  s.take<h16_t>((size_t)2 * cout * cin * 9);
-  s.take<unsigned>(1);
-  return s.off;
+  return split_prep_bytes((size_t)2 * cout * cin * 9);
 }
 YS_EXPORT size_t yolosod_conv3x3_prep_bytes(int cin) { return yolosod_conv3x3_prep_bytes_ex(cin, 64); }
 
@@ -1009,33 +949,12 @@ YS_EXPORT int yolosod_debug_conv3x3_form(int B, int cout, int H, int W) {
   return yolosod_debug_conv3x3_form_ex(B, 0, cout, H, W);
 }
 
-static bool conv3x3_carve(void* buf, size_t bytes, int cin, int cout, h16_t** wp, unsigned** flag) {
-  Carver cv(buf, bytes);
-  *wp = cv.take<h16_t>((size_t)2 * cout * cin * 9);
-  *flag = cv.take<unsigned>(1);
-  return *flag != nullptr;
-}
-
 // Weight preparation (re-run whenever the weights change): w [cout][cin][3][3] fp32 (BN folded) -> prep block.
 YS_EXPORT int yolosod_conv3x3_prepare_ex(const float* w, int cin, int cout, void* prep, size_t prep_bytes,
                                          void* stream) {
-  YS_CHECK_ARG(w && prep, "conv3x3_prepare: null pointer");
   YS_CHECK_ARG(yolosod_conv3x3_prep_bytes_ex(cin, cout) > 0, "conv3x3_prepare: (cin=%d, cout=%d) unsupported", cin,
                cout);
-  h16_t* wp;
-  unsigned* flag;
-  YS_CHECK_ARG(conv3x3_carve(prep, prep_bytes, cin, cout, &wp, &flag), "conv3x3_prepare: block too small (%zu)",
-               prep_bytes);
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(flag, 0, sizeof(unsigned), st) != hipSuccess) {
-    set_error("conv3x3_prepare: flag reset failed");
-    return -1;
-  }
-  const long n = (long)cout * cin * 9;
-  hipLaunchKernelGGL(c3::conv3x3_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, w, cin, cout, wp,
-                     range_flag_dev(), flag);
-  YS_CHECK_LAUNCH("conv3x3_prep");
-  return 0;
+  return split_prepare<9>("conv3x3_prepare", w, cin, cin, cout, prep, prep_bytes, stream);
 }
 YS_EXPORT int yolosod_conv3x3_prepare(const float* w, int cin, void* prep, size_t prep_bytes, void* stream) {
   return yolosod_conv3x3_prepare_ex(w, cin, 64, prep, prep_bytes, stream);
@@ -1058,12 +977,11 @@ YS_EXPORT int yolosod_conv3x3_silu_xs(const float* x, long x_bstride, float* y, 
   YS_CHECK_ARG(!res || (v4 && ((uintptr_t)res & 15) == 0 && res_bstride % 4 == 0 && res_bstride >= (long)cout * H * W),
                "conv3x3: the residual needs W %% 4 == 0 and 16-byte aligned images");
   if (B == 0) return 0;
-  h16_t* wp;
-  unsigned* flag;
-  YS_CHECK_ARG(conv3x3_carve(const_cast<void*>(prep), prep_bytes, cin, cout, &wp, &flag),
+  SplitPrep sp;
+  YS_CHECK_ARG(split_prep_carve(prep, prep_bytes, (size_t)2 * cout * cin * 9, &sp),
                "conv3x3: prepared block too small");
-  c3::Args a{x, wp, bias, y, y_bstride, res, res_bstride, cin, H, W, (W + c3::TW - 1) / c3::TW,
-             (H + c3::TH - 1) / c3::TH, cout / 16, range_flag_dev(), flag, 0, x_bstride};
+  c3::Args a{x, sp.wp, bias, y, y_bstride, res, res_bstride, cin, H, W, (W + c3::TW - 1) / c3::TW,
+             (H + c3::TH - 1) / c3::TH, cout / 16, range_flag_dev(), sp.flag, 0, x_bstride};
   const int ngrp = cout == 32 ? 1 : cout / 64;
   const long nwg = (long)B * a.tiles_x * a.tiles_y * ngrp;
   YS_CHECK_ARG(nwg < (1L << 31), "conv3x3: too many tiles");
@@ -1071,7 +989,7 @@ YS_EXPORT int yolosod_conv3x3_silu_xs(const float* x, long x_bstride, float* y, 
   // the persistent kernel for W % 4 == 0 (two workgroups per CU); the one-tile-per-workgroup kernel otherwise (and
   // for input images that are not 16-byte aligned, which the wide staging's loads need: no tensor of the model)
   const bool x16 = YS_C3_WIDE_STAGE == 0 || (((uintptr_t)x & 15) == 0 && x_bstride % 4 == 0);
-  if (v4 && x16 && g_c3_abl == 0) {
+  if (v4 && x16) {
     const int fgrp = g_c3_form >> 2;
     YS_CHECK_ARG(!(fgrp == 1 && cout == 32), "conv3x3: 32 outputs have no 64-channel group form");
     const int form = c3_form(B, cin, cout, H, W);
@@ -1081,11 +999,9 @@ YS_EXPORT int yolosod_conv3x3_silu_xs(const float* x, long x_bstride, float* y, 
     a.tiles_x = (W + C3_GEO_TW[geo] - 1) / C3_GEO_TW[geo];
     a.tiles_y = (H + C3_GEO_TH[geo] - 1) / C3_GEO_TH[geo];
     a.ntiles = (int)((long)B * a.tiles_x * a.tiles_y);
-    const long slots = 2L * c3_cu_count();
     const long nitems = (long)a.ntiles * (g32 ? cout / 32 : cout / 64);
     YS_CHECK_ARG(nitems < (1L << 31), "conv3x3: too many tiles");
-    long grid = slots < ((nitems + 7) / 8) * 8 ? slots : ((nitems + 7) / 8) * 8;
-    grid = (grid + 7) / 8 * 8;
+    const long grid = persistent_grid(2L * cu_count(), nitems);  // two workgroups per CU
     using KP = void (*)(c3::Args);
     static const KP kp[3][2][2] = {
         {{c3::conv3x3_p_kernel<0, 2, false>, c3::conv3x3_p_kernel<0, 2, true>},
@@ -1106,22 +1022,12 @@ YS_EXPORT int yolosod_conv3x3_silu_xs(const float* x, long x_bstride, float* y, 
     YS_CHECK_LAUNCH("conv3x3");
     return 0;
   }
-  auto kern = v4 ? c3::conv3x3_x2_kernel<0, true> : c3::conv3x3_x2_kernel<0, false>;
+  auto kern = v4 ? c3::conv3x3_x2_kernel<true> : c3::conv3x3_x2_kernel<false>;
   if (cout == 32) {
-    kern = res ? c3::conv3x3_x2_kernel<0, true, 1, true>
-               : (v4 ? c3::conv3x3_x2_kernel<0, true, 1, false> : c3::conv3x3_x2_kernel<0, false, 1, false>);
+    kern = res ? c3::conv3x3_x2_kernel<true, 1, true>
+               : (v4 ? c3::conv3x3_x2_kernel<true, 1, false> : c3::conv3x3_x2_kernel<false, 1, false>);
   } else if (res) {
-    kern = c3::conv3x3_x2_kernel<0, true, 2, true>;
-  } else if (cout == 64 && v4) {
-    switch (g_c3_abl) {  // timing ablations (W % 4 == 0 shapes, Cout 64)
-      case 1: kern = c3::conv3x3_x2_kernel<1, true>; break;
-      case 2: kern = c3::conv3x3_x2_kernel<2, true>; break;
-      case 4: kern = c3::conv3x3_x2_kernel<4, true>; break;
-      case 8: kern = c3::conv3x3_x2_kernel<8, true>; break;
-      case 12: kern = c3::conv3x3_x2_kernel<12, true>; break;
-      case 15: kern = c3::conv3x3_x2_kernel<15, true>; break;
-      default: break;
-    }
+    kern = c3::conv3x3_x2_kernel<true, 2, true>;
   }
   hipLaunchKernelGGL(kern, dim3((unsigned)nwg), dim3(256), 0, st, a);
   YS_CHECK_LAUNCH("conv3x3");
@@ -1178,19 +1084,16 @@ YS_EXPORT int yolosod_bottleneck3x3_silu_xs(const float* x, long x_bstride, floa
                    (!res || (((uintptr_t)res & 15) == 0 && res_bstride % 4 == 0)),
                "bottleneck3x3: images not 16-byte aligned");
   if (B == 0) return 0;
-  h16_t *wp1, *wp2;
-  unsigned *flag1, *flag2;
-  YS_CHECK_ARG(conv3x3_carve(const_cast<void*>(prep1), prep1_bytes, 32, 32, &wp1, &flag1) &&
-                   conv3x3_carve(const_cast<void*>(prep2), prep2_bytes, 32, 32, &wp2, &flag2),
+  SplitPrep sp1, sp2;
+  YS_CHECK_ARG(split_prep_carve(prep1, prep1_bytes, (size_t)2 * 32 * 32 * 9, &sp1) &&
+                   split_prep_carve(prep2, prep2_bytes, (size_t)2 * 32 * 32 * 9, &sp2),
                "bottleneck3x3: prepared block too small");
-  c3::BnArgs a{x, x_bstride, y, y_bstride, res, res_bstride, wp1, wp2, bias1, bias2, H, W, (W + c3::TW - 1) / c3::TW,
-               (H + c3::TH - 1) / c3::TH, 0, range_flag_dev(), flag1, flag2};
+  c3::BnArgs a{x, x_bstride, y, y_bstride, res, res_bstride, sp1.wp, sp2.wp, bias1, bias2, H, W,
+               (W + c3::TW - 1) / c3::TW, (H + c3::TH - 1) / c3::TH, 0, range_flag_dev(), sp1.flag, sp2.flag};
   const long ntiles = (long)B * a.tiles_x * a.tiles_y;
   YS_CHECK_ARG(ntiles < (1L << 31), "bottleneck3x3: too many tiles");
   a.ntiles = (int)ntiles;
-  const long slots = c3_cu_count();  // one workgroup per CU (LDS)
-  long grid = slots < (ntiles + 7) / 8 * 8 ? slots : (ntiles + 7) / 8 * 8;
-  grid = (grid + 7) / 8 * 8;
+  const long grid = persistent_grid(cu_count(), ntiles);  // one workgroup per CU (LDS)
   hipStream_t st = (hipStream_t)stream;
   if (res)
     hipLaunchKernelGGL(c3::bottleneck3x3_c32_kernel<true>, dim3((unsigned)grid), dim3(c3::BN_NT), 0, st, a);

@@ -43,6 +43,18 @@ unsigned* range_flag_dev() {
   unsigned* p = __atomic_load_n(&g_flags[dev], __ATOMIC_ACQUIRE);
   return p ? p : flag_alloc(dev);
 }
+
+int cu_count() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0, c = 0;
+    if (hipGetDevice(&dev) != hipSuccess ||
+        hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c <= 0)
+      c = 256;
+    n = c;
+  }
+  return n;
+}
 }  // namespace ys
 
 // Per-device initialisation of the library's device state (the split-range flag word); idempotent. Returns 0, or < 0

@@ -68,6 +68,12 @@ def _cached(mod: nn.Module, tag: str, srcs, make):
     return ent[1]
 
 
+def _prep(conv: nn.Module, tag: str, make):
+    """The zero-argument callable the ``_hip`` split-conv wrappers take for their prepared weight block:
+    ``make(conv.weight)`` (a ``_hip.*_prepare``) cached on ``conv`` under ``tag``."""
+    return lambda: _cached(conv, tag, (conv.weight,), lambda: make(conv.weight))
+
+
 def _cuda_device(v):
     if isinstance(v, torch.Tensor):
         return v.device if v.is_cuda else None
@@ -271,7 +277,7 @@ def _n1_stats_on(stats_layer) -> bool:
 
 def _n1_run(conv, x, out, out2, c2lo, n1, stats=None):
     """The fp16-split 1x1 kernel on a conv that conv_epilogue routed to it."""
-    prep = lambda: _cached(conv, "c1prep", (conv.weight,), lambda: _hip.conv1x1x2_prepare(conv.weight))  # noqa: E731
+    prep = _prep(conv, "c1prep", _hip.conv1x1x2_prepare)
     return _hip.conv1x1x2_silu(x, conv.bias, prep, conv.out_channels, out=out, out2=out2, c2lo=c2lo,
                                op="conv1x1x2_backbone" if n1 == "backbone" else "conv1x1x2", stats=stats)
 
@@ -311,7 +317,7 @@ def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, 
         x = x.materialize()
     if (split and act_code == 1 and out is None and res is None and stats is None and out2 is None and CONV3X3 != "0"
             and (CONV3X3 == "all" or tower) and _hip.conv3x3_ok(x, conv)):
-        prep = lambda: _cached(conv, "c3prep", (conv.weight,), lambda: _hip.conv3x3_prepare(conv.weight))  # noqa: E731
+        prep = _prep(conv, "c3prep", _hip.conv3x3_prepare)
         return _hip.conv3x3_silu(x, conv.bias, prep, conv.out_channels)
     if (split and _n1_on(n1, layer) and act_code == 1 and res is None
             and (stats is None or (n1 is True and out2 is None and stats in ("sum", "summax", "capool")
@@ -321,12 +327,12 @@ def conv_epilogue(conv: nn.Conv2d, act_code, x, out=None, res=None, stats=None, 
         return _n1_run(conv, x, out, out2, c2lo, n1, stats)
     if (split and _s1_on(s1) and act_code == 1 and stats is None and out2 is None and _hip.conv3x3_ok(x, conv)
             and x.shape[3] % 4 == 0 and (res is None or _hip._imgs_contig(res))):
-        prep = lambda: _cached(conv, "c3prep", (conv.weight,), lambda: _hip.conv3x3_prepare(conv.weight))  # noqa: E731
+        prep = _prep(conv, "c3prep", _hip.conv3x3_prepare)
         return _hip.conv3x3_silu(x, conv.bias, prep, conv.out_channels, out=out, res=res,
                                  op="conv3x3_backbone" if s1 == "backbone" else "conv3x3")
     if (split and _s2_on(s2, layer) and act_code == 1 and res is None and stats is None and out2 is None
             and _hip.conv3x3s2_ok(x, conv)):
-        prep = lambda: _cached(conv, "c3s2prep", (conv.weight,), lambda: _hip.conv3x3s2_prepare(conv.weight))  # noqa: E731
+        prep = _prep(conv, "c3s2prep", _hip.conv3x3s2_prepare)
         key = ("conv3x3s2_backbone", tuple(x.shape), (conv.out_channels, False, False)) if s2 == "backbone" else None
         return _hip.conv3x3s2_silu(x, conv.bias, prep, conv.out_channels, key=key, out=out)
     if (THIN1X1 and act_code == 1 and (stats is None or (stats in ("sum", "summax") and res is None and out2 is None))
@@ -419,7 +425,7 @@ class Conv(nn.Module):
         """SiLU(conv((x * gate_c) * gate_p) + b): the consumer of an SE (gate_c) / CBAM (gate_c = ca, gate_p = sa)
         whose output is never materialised (csrc/conv3x3s2.hip); ``key``: the op_timer key of the fused operator."""
         cv = self.conv
-        prep = lambda: _cached(cv, "c3s2prep", (cv.weight,), lambda: _hip.conv3x3s2_prepare(cv.weight))  # noqa: E731
+        prep = _prep(cv, "c3s2prep", _hip.conv3x3s2_prepare)
         return _hip.conv3x3s2_silu(x, cv.bias, prep, cv.out_channels, gate_c, gate_p, key=key)
 
     def forward_fuse(self, x, out=None, res=None, out2=None, c2lo=0):
@@ -495,8 +501,8 @@ class Bottleneck(nn.Module):
     def forward(self, x, out=None, out2=None):
         if self._one_launch(x, out, out2):
             c1, c2 = self.cv1.conv, self.cv2.conv
-            prep1 = lambda: _cached(c1, "c3prep", (c1.weight,), lambda: _hip.conv3x3_prepare(c1.weight))  # noqa: E731
-            prep2 = lambda: _cached(c2, "c3prep", (c2.weight,), lambda: _hip.conv3x3_prepare(c2.weight))  # noqa: E731
+            prep1 = _prep(c1, "c3prep", _hip.conv3x3_prepare)
+            prep2 = _prep(c2, "c3prep", _hip.conv3x3_prepare)
             backbone = self.cv2.s1_mark() == "backbone"
             return _hip.bottleneck3x3_silu(x, c1.bias, prep1, c2.bias, prep2, out=out, res=x if self.add else None,
                                            op="bottleneck3x3_backbone" if backbone else "bottleneck3x3")
