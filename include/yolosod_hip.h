@@ -300,6 +300,24 @@ int yolosod_bottleneck3x3_silu_xs(const float* x, long x_bstride, float* y, long
                                   size_t prep1_bytes, const float* bias2, const void* prep2, size_t prep2_bytes,
                                   void* stream);
 
+/* A Detect tower's last 3x3 conv (64 -> 64, BN folded, SiLU) with the tower's 1x1 conv and the decode in its epilogue:
+ * mode 1 the box tower (64 DFL logits -> rows 0 .. 3 of y: cx, cy, w, h), mode 2 the class tower (nc logits -> rows
+ * 4 .. 4 + nc - 1: scores), anchors a_off .. a_off + H*W - 1 of y [B][4 + nc][A]; the other elements of y are not
+ * written. The [B][64][H][W] feature map is never stored. Bit-identical to yolosod_conv3x3_silu_xs followed by
+ * yolosod_detect_head_levels on that level. prep: yolosod_conv3x3_prepare_ex(w, 64, 64, ...); head_prep:
+ * yolosod_detect_head_prepare of the 1x1 weight; head_bias [64] / [nc]. reg_max 16, 1 <= nc <= 16, W % 4 == 0 and
+ * 16-byte aligned images (image b at x + b*x_bstride); anything else is an error. The split-range flag reports the
+ * staged input, the features and both prepared blocks. The entry always runs the one launch;
+ * yolosod_debug_conv3x3_head_fused says when it is the routed choice. */
+int yolosod_conv3x3_head_xs(const float* x, long x_bstride, int B, int H, int W, const float* bias, const void* prep,
+                            size_t prep_bytes, const void* head_prep, const float* head_bias, int mode, int nc,
+                            float stride, float* y, int A, int a_off, void* stream);
+/* The prepared block of a tower's last 1x1 conv w [rows][64] (rows 64: box; 1 .. 16: class) for the entry above: the
+ * fp16 two-term split of 64 w in the head kernel's [t][s][g][row][i] planes (class rows past `rows` zero) and the
+ * block's range word, written once per parameter version. yolosod_detect_head_prep_bytes: its size (0: unsupported). */
+size_t yolosod_detect_head_prep_bytes(int rows);
+int yolosod_detect_head_prepare(const float* w, int rows, void* prep, size_t prep_bytes, void* stream);
+
 /* Thin fused 1x1 convolution of the backbone (conv.py:37-55 after fuse(), 1x1 case): out = SiLU(W x + bias) (+ res)
  * for Cout in {64, 128}, Cin in {64, 96, 128, 192, 256}, HW % 64 == 0; x / out / res may be channel slices (batch
  * strides, multiples of 4); out2 (optional, NULL) = packed copy of channels [c2lo, Cout). Other shapes: error. */
@@ -466,6 +484,13 @@ int yolosod_debug_bottleneck3x3_fused(int B, int H, int W);
 /* Test / measurement hook for the answer above: -1 automatic (default), 0 never, 1 every shape the kernel takes.
  * Other values are ignored. Returns the previous value. */
 int yolosod_debug_set_bottleneck3x3_fuse(int mode);
+/* Whether a Detect level with [B][64][H][W] tower maps is to run its towers' last convs as yolosod_conv3x3_head_xs (1)
+ * or as conv launches followed by the head kernel (0) under the current setting: automatically, when the 64 -> 64
+ * launch of that shape runs in 64-channel groups (yolosod_debug_conv3x3_form); never for W % 4 != 0. Host-side. */
+int yolosod_debug_conv3x3_head_fused(int B, int H, int W);
+/* Test / measurement hook for the answer above: -1 automatic (default), 0 never, 1 every shape the kernel takes.
+ * Other values are ignored. Returns the previous value. */
+int yolosod_debug_set_conv3x3_head_fuse(int mode);
 void yolosod_debug_set_gemm_x2(int on);
 /* Test hook: the bf16 decomposed SwinBlock's depthwise conv + token layout and LN1 in one pass
  * (swin_tokens_ln_bf16_kernel, 1, default) or as two kernels (0);

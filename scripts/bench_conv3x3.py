@@ -1,7 +1,7 @@
 """Micro-benchmark: the stride-1 3x3 convs of the n640 step (bs 32) - the Detect towers and the backbone's / neck's C2f
 Bottleneck convs (Cout 32 .. 256, with and without the shortcut) - on the fp16-split kernel vs MIOpen (F.conv2d without
 bias + the HIP bias / SiLU (+ shortcut) epilogue, as the executor runs it). GPU only.
-python scripts/bench_conv3x3.py [forms | bottleneck [H [batches]]]; YOLOSOD_LIB_AB=<lib> times another build of the library."""
+python scripts/bench_conv3x3.py [forms | bottleneck [H [batches]] | head [rounds]]; YOLOSOD_LIB_AB=<lib> times another build of the library."""
 import sys
 from pathlib import Path
 
@@ -60,6 +60,64 @@ if len(sys.argv) > 1 and sys.argv[1] == "bottleneck":
         print(f"B {B:2d} x 32 x {H}^2 ({mb:6.1f} MB/map) equal {same}  " + "   ".join(
             f"fused {f:.4f}  cv1 {a:.4f} + cv2 {b:.4f} = {a + b:.4f}  pair back-to-back {p:.4f} ms"
             for f, a, b, p in row), flush=True)
+    sys.exit(0)
+
+if len(sys.argv) > 1 and sys.argv[1] == "head":
+    # a Detect level's two towers from their second conv on: the two fused launches (conv + 1x1 conv + decode, box and
+    # class) against the two conv launches + the head kernel on that level alone, alternating the sides, four timings
+    # per side; the spread is the largest difference between two timings of one side at one size.
+    # python scripts/bench_conv3x3.py head [rounds]
+    rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 4
+    nc, strides = 10, [4.0, 8.0, 16.0, 32.0]
+    rows, spread = [], 0.0
+    for B, H, li in ((32, 160, 0), (32, 80, 1), (32, 40, 2), (32, 20, 3), (8, 320, 0)):
+        x = torch.randn(B, 64, H, H, device=dev)
+        ws = [torch.randn(64, 64, 3, 3, device=dev) * 0.04 for _ in range(2)]
+        bs = [torch.randn(64, device=dev) * 0.1 for _ in range(2)]
+        hw = [torch.randn(64, 64, device=dev) * 0.25, torch.randn(nc, 64, device=dev) * 0.2]
+        hb = [torch.randn(64, device=dev), torch.randn(nc, device=dev) - 2.0]
+        ps = [_hip.conv3x3_prepare(w) for w in ws]
+        hps = [_hip.detect_head_prepare(hw[0], 64), _hip.detect_head_prepare(hw[1], nc)]
+        sizes = [(4, 4)] * 4
+        sizes[li] = (H, H)
+        a_off = 16 * li
+        A = 16 * 3 + H * H
+        y = torch.full((B, 4 + nc, A), float("nan"), device=dev)
+        fb, fc = (torch.empty(B, 64, H, H, device=dev) for _ in range(2))
+        fbs = [fb if i == li else sizes[i] for i in range(4)]
+        fcs = [fc if i == li else None for i in range(4)]
+
+        def pair():
+            _hip.conv3x3_silu(x, bs[0], lambda: ps[0], 64, out=fb)
+            _hip.conv3x3_silu(x, bs[1], lambda: ps[1], 64, out=fc)
+            _hip.detect_head_into(y, li, li + 1, fbs, fcs, [hw[0]] * 4, [hb[0]] * 4, [hw[1]] * 4, [hb[1]] * 4, strides, nc)
+
+        def fused():
+            for m in (1, 2):
+                _hip.conv3x3_head(x, bs[m - 1], lambda: ps[m - 1], lambda: hps[m - 1], hb[m - 1], m, nc, strides[li], y,
+                                  a_off)
+
+        auto = _hip.conv3x3_head_fused(B, H, H)
+        # the fused side runs 64-channel groups on every shape; the conv side its automatic form
+        pair()
+        y0 = y.clone()
+        y.fill_(float("nan"))
+        fused()
+        same = torch.equal(torch.nan_to_num(y, nan=-1.0), torch.nan_to_num(y0, nan=-1.0))
+        for _ in range(3):  # both sides warm (clocks, caches, the allocator) before the first timing
+            timed(fused, 20), timed(pair, 20)
+        tf, tp = [], []
+        for _ in range(rounds):
+            tf.append(timed(fused))
+            tp.append(timed(pair))
+        spread = max(spread, max(tf) - min(tf), max(tp) - min(tp))
+        rows.append((B, H, auto, same, tf, tp))
+    print(f"spread (largest difference between two timings of one side at one size): {spread:.4f} ms")
+    for B, H, auto, same, tf, tp in rows:
+        wins = min(tp) - max(tf) > spread
+        print(f"B {B:2d} x 64 x {H:3d}^2  equal {same}  automatic route {'fused' if auto else 'pair '}  "
+              f"fused {' '.join(f'{t:.4f}' for t in tf)}   conv + conv + head {' '.join(f'{t:.4f}' for t in tp)} ms   "
+              f"every fused timing beats every pair timing by more than the spread: {wins}", flush=True)
     sys.exit(0)
 
 # every stride-1 3x3 launch shape of the n640 step at bs 32: (input shape, Cout, residual). Detect towers (Cout 64),

@@ -2,7 +2,9 @@
 python scripts/c3_pmc.py [cin cout [form]]   (default 64 64: the P2 Detect tower conv; 32 32: layer 3 / layer 27;
 form: yolosod_debug_set_conv3x3_form, 0 = the automatic choice), or
 python scripts/c3_pmc.py bottleneck fused|pair [B]   the 32-channel Bottleneck with the shortcut in place in a
-96-channel buffer, as one launch or as its two conv launches. GPU only."""
+96-channel buffer, as one launch or as its two conv launches, or
+python scripts/c3_pmc.py head fused|pair   the P2 box tower's last conv with the head's tail in its epilogue, or the conv
+launch followed by the head kernel on that level. GPU only."""
 import sys
 from pathlib import Path
 
@@ -28,6 +30,27 @@ if len(sys.argv) > 2 and sys.argv[1] == "bottleneck":
         else:
             _hip.conv3x3_silu(x, b1, lambda: p1, 32, out=t)
             _hip.conv3x3_silu(t, b2, lambda: p2, 32, out=y, res=x)
+    torch.cuda.synchronize()
+    print("ok")
+    sys.exit(0)
+if len(sys.argv) > 2 and sys.argv[1] == "head":
+    # the P2 box tower from its second conv on: the fused launch (conv + 1x1 conv + decode), or the conv launch and the
+    # head kernel on that level (which also reads the class features: half of its traffic is the box tower's)
+    B, H, W, nc = 32, 160, 160, 10
+    x = torch.randn(B, 64, H, W, device=dev)
+    w = torch.randn(64, 64, 3, 3, device=dev) * 0.04
+    b = torch.randn(64, device=dev) * 0.1
+    hw, hb = torch.randn(64, 64, device=dev) * 0.25, torch.randn(64, device=dev)
+    cw, cb = torch.randn(nc, 64, device=dev) * 0.2, torch.randn(nc, device=dev) - 2.0
+    p, hp = _hip.conv3x3_prepare(w), _hip.detect_head_prepare(hw, 64)
+    y = torch.empty(B, 4 + nc, H * W, device=dev)
+    fb, fc = torch.empty(B, 64, H, W, device=dev), torch.randn(B, 64, H, W, device=dev)
+    for _ in range(5):
+        if sys.argv[2] == "fused":
+            _hip.conv3x3_head(x, b, lambda: p, lambda: hp, hb, 1, nc, 4.0, y, 0)
+        else:
+            _hip.conv3x3_silu(x, b, lambda: p, 64, out=fb)
+            _hip.detect_head_into(y, 0, 1, [fb], [fc], [hw], [hb], [cw], [cb], [4.0], nc)
     torch.cuda.synchronize()
     print("ok")
     sys.exit(0)

@@ -111,6 +111,11 @@ SIGNATURES = {
     "yolosod_debug_conv3x3_form": (_i, [_i, _i, _i, _i]),
     "yolosod_debug_conv3x3_form_ex": (_i, [_i, _i, _i, _i, _i]),
     "yolosod_bottleneck3x3_silu_xs": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _sz, _vp]),
+    "yolosod_conv3x3_head_xs": (_i, [_vp, _l, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _i, _i, _f, _vp, _i, _i, _vp]),
+    "yolosod_detect_head_prep_bytes": (_sz, [_i]),
+    "yolosod_detect_head_prepare": (_i, [_vp, _i, _vp, _sz, _vp]),
+    "yolosod_debug_conv3x3_head_fused": (_i, [_i, _i, _i]),
+    "yolosod_debug_set_conv3x3_head_fuse": (_i, [_i]),
     "yolosod_debug_bottleneck3x3_fused": (_i, [_i, _i, _i]),
     "yolosod_debug_set_bottleneck3x3_fuse": (_i, [_i]),
     "yolosod_debug_set_conv1x1x2_form": (_i, [_i]),
@@ -593,13 +598,58 @@ def detect_head(box_feats, cls_feats, box_w, box_b, cls_w, cls_b, strides, nc, r
 def detect_head_into(y, l0, l1, box_feats, cls_feats, box_w, box_b, cls_w, cls_b, strides, nc, reg_max=16):
     """``detect_head`` for levels [l0, l1) only, into y [B, 4+nc, A] laid out for all levels (torch.ops.yolosod.
     detect_head_into): the executor decodes the levels whose towers are done while the last level's still run."""
+    if any(not isinstance(t, torch.Tensor) for t in box_feats):
+        return _detect_head_into_sized(y, l0, l1, box_feats, cls_feats, box_w, box_b, cls_w, cls_b, strides, nc, reg_max)
     bf = _act_dtype(_t(box_feats[0], "box_feats[0]"))
     B, c2 = box_feats[0].shape[:2]
     c3 = cls_feats[0].shape[1]
-    A = sum(t.shape[2] * t.shape[3] for t in box_feats[l0:l1])
+    A = sum(t.shape[2] * t.shape[3] for t in box_feats[l0:l1])  # the anchors this launch decodes (perf.op_cost)
     _launch(("head", (B, A), (nc, c2, c3)) + ((2,) if bf else ()), box_feats[0].device, ops().detect_head_into, y,
             int(l0), int(l1), list(box_feats), list(cls_feats), list(box_w), list(box_b), list(cls_w), list(cls_b),
             [float(s) for s in strides], int(nc), int(reg_max))
+    return y
+
+
+def _detect_head_into_sized(y, l0, l1, box_feats, cls_feats, box_w, box_b, cls_w, cls_b, strides, nc, reg_max):
+    """detect_head_into when a level outside [l0, l1) has no tower features (a level whose tower convs decoded it
+    themselves, conv3x3_head): its entry of box_feats is its map size (H, W) and its entry of cls_feats is ignored.
+    fp32 features; straight on the C ABI (yolosod_detect_head_levels), since the registered op takes tensors only."""
+    lib = load_library()
+    nl = len(box_feats)
+    if not (0 <= l0 < l1 <= nl) or any(not isinstance(box_feats[i], torch.Tensor) for i in range(l0, l1)):
+        raise RuntimeError(f"detect_head_into: levels [{l0}, {l1}) need their tower features")
+    f0 = box_feats[l0]
+    B, c2 = f0.shape[:2]
+    c3 = cls_feats[l0].shape[1]
+    hs, ws, keep = [], [], []
+    fb, fc, pw = ((ctypes.c_void_p * nl)() for _ in range(3))
+    pb, cw, cb = ((ctypes.c_void_p * nl)() for _ in range(3))
+    for i in range(nl):
+        if isinstance(box_feats[i], torch.Tensor):
+            hs.append(int(box_feats[i].shape[2]))
+            ws.append(int(box_feats[i].shape[3]))
+        else:
+            hs.append(int(box_feats[i][0]))
+            ws.append(int(box_feats[i][1]))
+        if l0 <= i < l1:
+            if tuple(box_feats[i].shape[:2]) != (B, c2) or tuple(cls_feats[i].shape) != (B, c3, hs[i], ws[i]):
+                raise RuntimeError(f"detect_head_into: level {i} features {tuple(box_feats[i].shape)} / "
+                                   f"{tuple(cls_feats[i].shape)} mismatch")
+            ts = (box_feats[i], cls_feats[i], box_w[i], box_b[i], cls_w[i], cls_b[i])
+            ne = (None, None, 64 * c2, 64, nc * c3, nc)
+            for arr, t, n in zip((fb, fc, pw, pb, cw, cb), ts, ne):
+                arr[i] = _p(t, f"detect_head_into: level {i}", n)
+            keep.append(ts)
+    A = sum(h * w for h, w in zip(hs, ws))
+    if (y.dtype != torch.float32 or not y.is_contiguous() or tuple(y.shape) != (B, 4 + nc, A)
+            or y.device != f0.device):
+        raise RuntimeError(f"detect_head_into: y {tuple(y.shape)} is not a contiguous fp32 [{B}, {4 + nc}, {A}] tensor")
+    Al = sum(hs[i] * ws[i] for i in range(l0, l1))  # the anchors this launch decodes (perf.op_cost)
+    ih, iw = (ctypes.c_int * nl)(*hs), (ctypes.c_int * nl)(*ws)
+    st = (ctypes.c_float * nl)(*[float(s) for s in strides])
+    _check(_launch(("head", (B, Al), (nc, c2, c3)), f0.device, lib.yolosod_detect_head_levels, nl, int(l0), int(l1),
+                   fb, fc, int(c2), int(c3), pw, pb, cw, cb, ih, iw, st, int(B), int(nc), int(reg_max), y.data_ptr(),
+                   0, _stream(f0.device)), "detect_head_into")
     return y
 
 
@@ -918,6 +968,54 @@ def conv3x3_silu(x, bias, prep, cout=64, out=None, res=None, op="conv3x3"):
                                            blk.data_ptr(), blk.numel(), _stream(x.device))
 
     _check(_launch((op, tuple(x.shape), cout if res is None else (cout, "res")), x.device, run), "conv3x3")
+    return y
+
+
+def conv3x3_head_fused(B, H, W) -> bool:
+    """Whether a Detect level with [B, 64, H, W] tower maps runs its towers' last convs with the head's tail in their
+    epilogue (yolosod_debug_conv3x3_head_fused: the shapes whose 64 -> 64 launch runs in 64-channel groups, or the
+    route forced by yolosod_debug_set_conv3x3_head_fuse)."""
+    return bool(load_library().yolosod_debug_conv3x3_head_fused(int(B), int(H), int(W)))
+
+
+def detect_head_prepare(w, rows):
+    """Prepared block (uint8 tensor) of a tower's last 1x1 conv weight ``w`` [rows, 64(, 1, 1)] for conv3x3_head."""
+    lib = load_library()
+    nbytes = int(lib.yolosod_detect_head_prep_bytes(int(rows)))
+    wc = w.detach().float().reshape(w.shape[0], -1).contiguous()
+    if nbytes == 0 or tuple(wc.shape) != (rows, 64):
+        raise RuntimeError(f"detect_head_prepare: weight {tuple(w.shape)} unsupported ([64 | 1..16, 64])")
+    blk = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    _check(_launch(("head_prep", (rows, 64), None), w.device, lib.yolosod_detect_head_prepare, _dev(wc, "weight"),
+                   int(rows), blk.data_ptr(), nbytes, _stream(w.device)), "detect_head_prepare")
+    return blk
+
+
+def conv3x3_head(x, bias, prep, head_prep, head_bias, mode, nc, stride, y, a_off):
+    """A Detect tower's last 3x3 conv (64 -> 64) + its 1x1 conv + the decode in one launch (csrc/conv3x3.hip,
+    conv3x3_head_kernel), bit-identical to conv3x3_silu followed by detect_head_into on that level: ``mode`` 1 writes
+    the box rows 0 .. 3, 2 the class rows 4 .. 4 + nc - 1, of anchors [a_off, a_off + H W) of y [B, 4 + nc, A]. ``prep``
+    / ``head_prep``: callables returning the cached prepared blocks (conv3x3_prepare / detect_head_prepare)."""
+    lib = load_library()
+    B, Cin, H, W = x.shape
+    if Cin != 64:
+        raise RuntimeError(f"conv3x3_head: {Cin} channels (64 only)")
+    if (y.dtype != torch.float32 or y.device != x.device or not y.is_contiguous() or y.dim() != 3 or y.shape[0] != B
+            or y.shape[1] != 4 + nc):
+        raise RuntimeError(f"conv3x3_head: y {tuple(y.shape)} is not a contiguous fp32 [{B}, {4 + nc}, A] tensor")
+    b = bias.detach().float().contiguous()
+    hb = head_bias.detach().float().contiguous()
+    if hb.numel() != (64 if mode == 1 else nc):
+        raise RuntimeError(f"conv3x3_head: head bias of {hb.numel()} values")
+
+    def run():
+        blk, hblk = prep(), head_prep()
+        _img_view(x, (B, 64, H, W), "conv3x3_head: x")
+        return lib.yolosod_conv3x3_head_xs(x.data_ptr(), x.stride(0), B, H, W, _dev(b, "bias"), blk.data_ptr(),
+                                           blk.numel(), hblk.data_ptr(), _dev(hb, "head bias"), int(mode), int(nc),
+                                           float(stride), y.data_ptr(), int(y.shape[2]), int(a_off), _stream(x.device))
+
+    _check(_launch(("conv3x3", tuple(x.shape), (64, "head", int(mode))), x.device, run), "conv3x3_head")
     return y
 
 

@@ -19,6 +19,7 @@
 // fragments (LDS) per tap. The pixels are the MFMA's A operand, so a lane's accumulators are 4 consecutive pixels of
 // one channel (16-byte stores). The next chunk's halo loads are spread over the current chunk's taps.
 #include "split_conv.h"
+#include "detect_head_math.h"
 
 namespace ys {
 namespace c3 {
@@ -47,6 +48,18 @@ struct Args {
   const unsigned* prep_flag;
   int ntiles;          // persistent kernel: B tiles_y tiles_x
   long xbs;            // image b of x at x + b xbs (>= cin H W: x may be a channel slice of a concat buffer)
+};
+
+// conv3x3_head_kernel's arguments: the conv's (y / ybs / res unused) and the head tail's. A type of its own, so that
+// the kernels above keep their argument block.
+struct HeadTailArgs : Args {
+  const h16_t* hw;        // the 1x1 conv's planes (yolosod_detect_head_prepare): hi [t][s][g][row][i], then lo
+  const unsigned* hflag;  // their block's range word
+  const float* hbias;     // [64] box / [nc] class
+  float* hy;              // the level's first anchor of image 0, row 0 of y [B][4 + nc][A]
+  long hbs;               // (4 + nc) A
+  int A, nc;
+  float stride;
 };
 
 // One tile per workgroup (the shapes the persistent form below does not take). V4: W % 4 == 0 (16-byte stores).
@@ -285,6 +298,14 @@ struct GeoD : Geo<G> {
 #define YS_C3_WIDE_STAGE 1
 #endif
 
+// The head tail's feature tile (conv3x3_head_kernel): fp32 [pixel][HT_RS] for the tile's 16 blocks of 16 pixels,
+// channel c of pixel px at column c ^ ((px & 8) >> 2). With 68-float rows and that swizzle both sides are free of bank
+// conflicts (banks of 4 bytes mod 32 per 32-lane half, tests/test_conv3x3_head_isa.py enumerates them): the conv's
+// lanes (g, l15) write channel l15 of pixels 4 g .. + 3 (a half holds two g: rows 4 x 68 = 16 banks apart), the tail's
+// lanes (g, j) read channels g + 4 q of pixel j (rows 4 banks apart, the swizzle moves pixels 8 .. 15 two banks on).
+constexpr int HT_RS = 68;
+constexpr int HT_HALVES = 256 * HT_RS * 2;
+
 // F: the wave layout / weight path of a 32-channel output group (CBW == 1; every F is bit-identical, see above).
 //   F 0: wave w = (row-half w >> 1: 8 block slots) x (channel block w & 1); weight fragments from L2, one tap ahead.
 //   F 1: F 0's layout with the wave's whole weight set (9 taps x 2 planes: 72 VGPRs) loaded once before the item
@@ -292,9 +313,12 @@ struct GeoD : Geo<G> {
 //        load, so the only vector-memory loads in flight in it are the next iteration's halo.
 //   F 2: wave w = block slots 4 w .. 4 w + 3 x both channel blocks: a pixel fragment read from LDS feeds six MFMAs
 //        instead of three (8 ds_read_b128 per wave and tap instead of 16); weight fragments from L2, one tap ahead.
-template <int G, int CBW, bool RES, int F>
-__device__ __forceinline__ void conv3x3_p_body(const Args& p) {
+// MODE (conv3x3_head_kernel below; 0: none, the kernels of this section): the Detect head's tail in the epilogue, on
+// AT = HeadTailArgs.
+template <int G, int CBW, bool RES, int F, int MODE = 0, class AT = Args>
+__device__ __forceinline__ void conv3x3_p_body(const AT& p) {
   static_assert(F == 0 || CBW == 1, "conv3x3: F 1 / F 2 are forms of the 32-channel group");
+  static_assert(MODE == 0 || (F == 0 && CBW == 2 && !RES), "conv3x3: the head tail needs a pixel's 64 channels");
   constexpr int NS = F == 2 ? 4 : 8;    // block slots per wave
   constexpr int CW = F == 2 ? 2 : CBW;  // 16-channel blocks per wave
   using Ge = GeoD<G>;
@@ -303,13 +327,18 @@ __device__ __forceinline__ void conv3x3_p_body(const Args& p) {
   constexpr bool WIDE = YS_C3_WIDE_STAGE != 0;
   constexpr int NMG = Ge::NMG, NMID = Ge::NMID;
   constexpr int NQUAD = WIDE ? Ge::NWQ : Ge::NQUAD, NIT = WIDE ? Ge::NITW : Ge::NIT;
-  __shared__ __attribute__((aligned(16))) h16_t Pl[2 * PL];
+  // MODE: the planes' memory also holds the tile's fp32 features between the conv and the head tail
+  constexpr int PLN = MODE != 0 && HT_HALVES > 2 * PL ? HT_HALVES : 2 * PL;
+  __shared__ __attribute__((aligned(16))) h16_t Pl[PLN];
   __shared__ float bsh[512];  // every output channel's bias: an epilogue load would wait behind the prefetches
   const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l15 = lane & 15, g = lane >> 4;
   const int H = p.H, W = p.W, HWi = H * W, nq = F == 1 ? 1 : p.cin >> 5;
   float rng = 0.f;
   for (int o = tid; o < 16 * p.ncb_all; o += 256) bsh[o] = p.bias[o];  // ordered before use by the loop's barriers
+  if constexpr (MODE != 0) {  // the 1x1 conv's bias behind the conv's 64
+    if (tid < 64) bsh[64 + tid] = tid < (MODE == 1 ? 64 : p.nc) ? p.hbias[tid] : 0.f;
+  }
 
   const int ngrp = p.ncb_all / (2 * CBW);
   const int nj = gridDim.x >> 3, j = blockIdx.x >> 3, xcd = blockIdx.x & 7;
@@ -327,6 +356,8 @@ __device__ __forceinline__ void conv3x3_p_body(const Args& p) {
         (short)0, __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
   };
   const __amdgpu_buffer_rsrc_t rw = rsrc(p.wp, (unsigned)(9L * nq * p.ncb_all * 2 * 1024));
+  __amdgpu_buffer_rsrc_t rhw;
+  if constexpr (MODE != 0) rhw = rsrc(p.hw, (unsigned)((MODE == 1 ? 4 : 1) * 4 * 1024));
   int pk[NIT], el0[NIT];
 #pragma unroll
   for (int i = 0; i < NIT; ++i) {
@@ -546,7 +577,81 @@ __device__ __forceinline__ void conv3x3_p_body(const Args& p) {
         }
       }
     }
-    if (r.q == nq - 1) {
+    if constexpr (MODE != 0) {
+      // The head's tail instead of the store (detect_head_math.h: detect_head_x2_kernel's arithmetic on the same
+      // operands, so the same bits as the store followed by that kernel). The tile's features go through LDS as the
+      // fp32 values the store would have written; wave w then takes blocks 4 w .. 4 w + 3 with all 64 channels.
+      if (r.q == nq - 1) {
+        constexpr int NHT = MODE == 1 ? 4 : 1;  // 16-row output tiles: 4 x 16 DFL bins / the classes
+        float bv[CW];
+#pragma unroll
+        for (int u = 0; u < CW; ++u) bv[u] = bsh[16 * (cbw0 + u) + l15];
+#pragma unroll
+        for (int cb = 0; cb < NS; ++cb)
+#pragma unroll
+          for (int u = 0; u < CW; ++u)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[u][cb][e] = silu_fast_(acc[u][cb][e] * (1.0f / WSC) + bv[u]);
+        __syncthreads();  // every wave is done with the planes
+        float* T = reinterpret_cast<float*>(Pl);
+#pragma unroll
+        for (int cb = 0; cb < NS; ++cb)
+#pragma unroll
+          for (int u = 0; u < CW; ++u) {
+            const int col = (16 * (cbw0 + u) + l15) ^ (g & 2);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) T[((slot0 + cb) * 16 + 4 * g + e) * HT_RS + col] = acc[u][cb][e];
+            acc[u][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+          }
+        // the 1x1 conv's fragments, L2-hot, in flight across the barrier (issued once the accumulators'
+        // registers are free)
+        f16x8_t hwf[NHT * 2][2];
+#pragma unroll
+        for (int idx = 0; idx < NHT * 2; ++idx)
+#pragma unroll
+          for (int pl = 0; pl < 2; ++pl)
+            hwf[idx][pl] = __builtin_bit_cast(
+                f16x8_t, __builtin_amdgcn_raw_buffer_load_b128(
+                             rhw, (unsigned)(((pl * NHT * 2 + idx) * 64 + lane) * 16), 0, 0));
+        __syncthreads();
+        float* yb = p.hy + (long)r.b * p.hbs;
+        const int j = l15, sw = (j & 8) >> 2;
+#pragma unroll 1
+        for (int k = 0; k < 4; ++k) {
+          const int blk = 4 * wid + k;  // wave-uniform
+          if (NBLK < 16 && blk >= NBLK) break;
+          const int oy = r.ty * TH + (blk / TBX) * BH + j / BW, ox = r.tx * TW + (blk % TBX) * BW + j % BW;
+          const bool ok = oy < H && ox < W;
+          const float* tp = T + (blk * 16 + j) * HT_RS;
+          float c[16];  // channels g + 4 q of pixel j; a pixel outside the image: zeros, as a load past the level's end
+#pragma unroll
+          for (int q = 0; q < 16; ++q) {
+            const float v = tp[(g + 4 * q) ^ sw];
+            c[q] = ok ? v : 0.f;
+          }
+          f32x4 ha[NHT];
+#pragma unroll
+          for (int t = 0; t < NHT; ++t) ha[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+          headm::mma<NHT, 2>(c, [&](int idx, int pl) { return hwf[idx][pl]; }, ha, rng);
+          const int pa = oy * W + ox;
+          if constexpr (MODE == 1) {
+            float bb[4][4], dist[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t)
+#pragma unroll
+              for (int e = 0; e < 4; ++e) bb[t][e] = bsh[64 + 16 * t + 4 * g + e];
+            headm::dfl(ha, bb, g, dist);
+            if (ok) yb[(long)g * p.A + pa] = headm::box_out(dist, ox, oy, p.stride, g);
+          } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const int c1 = 4 * g + e;
+              if (ok && c1 < p.nc) yb[(long)(4 + c1) * p.A + pa] = headm::cls_out(ha[0][e], bsh[64 + c1]);
+            }
+          }
+        }
+      }
+    } else if (r.q == nq - 1) {
       float* yb = p.y + (long)r.b * p.ybs;
       float bv[CW];
 #pragma unroll
@@ -574,11 +679,23 @@ __device__ __forceinline__ void conv3x3_p_body(const Args& p) {
   }
   range_report(p.range_flag, rng);
   if (p.prep_flag && p.range_flag && blockIdx.x == 0 && threadIdx.x == 0 && *p.prep_flag) *p.range_flag = 1u;
+  if constexpr (MODE != 0) {
+    if (p.hflag && p.range_flag && blockIdx.x == 0 && threadIdx.x == 0 && *p.hflag) *p.range_flag = 1u;
+  }
 }
 
 template <int G, int CBW, bool RES>
 __global__ __launch_bounds__(256, 2) void conv3x3_p_kernel(Args p) {
   conv3x3_p_body<G, CBW, RES, 0>(p);
+}
+
+// A Detect tower's last 3x3 conv (64 -> 64) with the tower's 1x1 conv and the decode in its epilogue instead of the
+// store: MODE 1 the box tower (64 DFL logits -> cx, cy, w, h of y), MODE 2 the class tower (nc <= 16 logits -> scores).
+// The [B, 64, H, W] feature map is never written; the result is bit-identical to conv3x3_p_kernel<G, 2, false>
+// followed by detect_head_x2_kernel on that level (the same operands through the same expressions, detect_head_math.h).
+template <int G, int MODE>
+__global__ __launch_bounds__(256, 2) void conv3x3_head_kernel(HeadTailArgs p) {
+  conv3x3_p_body<G, 2, false, 0, MODE, HeadTailArgs>(p);
 }
 
 // The F 1 / F 2 forms of the 32-channel group (Cout 32: layer 3's and the neck's P2 Bottleneck convs).
@@ -1040,6 +1157,73 @@ YS_EXPORT int yolosod_conv3x3_silu_ex(const float* x, float* y, long y_bstride, 
                                       size_t prep_bytes, void* stream) {
   return yolosod_conv3x3_silu_xs(x, (long)cin * H * W, y, y_bstride, res, res_bstride, B, cin, cout, H, W, bias, prep,
                                  prep_bytes, stream);
+}
+
+// ---- a Detect tower's last conv with the head's tail (64 -> 64 -> decode) -------------------------------------------
+// Routing (callers ask yolosod_debug_conv3x3_head_fused; the entry below always runs the fused kernel): automatic (-1)
+// fuses a level when its 64 -> 64 launch runs in 64-channel groups (c3_form: at least two workgroup slots per CU worth
+// of tiles); a 32-channel group holds half of a pixel's channels and cannot run the tail. 0: never; 1: every shape the
+// kernel takes. yolosod_debug_set_conv3x3_head_fuse returns the previous value.
+static int g_head_fuse = -1;
+YS_EXPORT int yolosod_debug_set_conv3x3_head_fuse(int mode) {
+  const int old = g_head_fuse;
+  if (mode >= -1 && mode <= 1) g_head_fuse = mode;
+  return old;
+}
+
+static bool head_tail_shape_ok(int B, int H, int W) {
+  return B > 0 && H > 0 && W > 0 && W % 4 == 0 && 64L * H * W * 4 < (1L << 31);
+}
+
+YS_EXPORT int yolosod_debug_conv3x3_head_fused(int B, int H, int W) {
+  if (!head_tail_shape_ok(B, H, W) || g_head_fuse == 0) return 0;
+  return g_head_fuse == 1 || (c3_form(B, 64, 64, H, W) >> 2) == 1;
+}
+
+// The box (mode 1) or class (mode 2) tower's tail in one launch: SiLU(conv3x3(x, W) + bias), 64 -> 64, then the
+// tower's 1x1 conv (head_prep: yolosod_detect_head_prepare of W [64][64] / [nc][64]; head_bias [64] / [nc]) and the
+// decode, into rows 0 .. 3 (mode 1) or 4 .. 4 + nc - 1 (mode 2), anchors a_off .. a_off + H W - 1, of y [B][4 + nc][A].
+// Image b of x ([64][H][W], 16-byte aligned) at x + b x_bstride; W % 4 == 0; reg_max 16; 1 <= nc <= 16. The geometry
+// is the conv's (the forced field of yolosod_debug_set_conv3x3_form, or the automatic choice); the groups are always
+// of 64 channels. Bit-identical to yolosod_conv3x3_silu_xs followed by yolosod_detect_head_levels on that level.
+YS_EXPORT int yolosod_conv3x3_head_xs(const float* x, long x_bstride, int B, int H, int W, const float* bias,
+                                      const void* prep, size_t prep_bytes, const void* head_prep,
+                                      const float* head_bias, int mode, int nc, float stride, float* y, int A, int a_off,
+                                      void* stream) {
+  YS_CHECK_ARG(x && bias && prep && head_prep && head_bias && y, "conv3x3_head: null pointer");
+  YS_CHECK_ARG(mode == 1 || mode == 2, "conv3x3_head: mode=%d (1 box, 2 class)", mode);
+  YS_CHECK_ARG(nc >= 1 && nc <= 16, "conv3x3_head: nc=%d unsupported (1..16)", nc);
+  YS_CHECK_ARG(B >= 0 && H > 0 && W > 0 && W % 4 == 0, "conv3x3_head: bad shape (W %% 4 == 0 only)");
+  YS_CHECK_ARG(64L * H * W * 4 < (1L << 31), "conv3x3_head: plane too large");
+  YS_CHECK_ARG(x_bstride >= 64L * H * W && ((uintptr_t)x & 15) == 0 && x_bstride % 4 == 0,
+               "conv3x3_head: input images must be 16-byte aligned, batch stride >= %ld", 64L * H * W);
+  YS_CHECK_ARG(a_off >= 0 && A > 0 && (long)a_off + (long)H * W <= A, "conv3x3_head: anchors [%d, %ld) outside [0, %d)",
+               a_off, (long)a_off + (long)H * W, A);
+  YS_CHECK_ARG((long)B * (4 + nc) * A < (1L << 40), "conv3x3_head: output too large");
+  if (B == 0) return 0;
+  SplitPrep sp, hp;
+  YS_CHECK_ARG(split_prep_carve(prep, prep_bytes, (size_t)2 * 64 * 64 * 9, &sp), "conv3x3_head: prepared block too small");
+  const size_t hhalves = (size_t)2 * (mode == 1 ? 4 : 1) * 1024;
+  split_prep_carve(head_prep, split_prep_bytes(hhalves), hhalves, &hp);
+  const int geo = (c3_form(B, 64, 64, H, W) & 3) - 1;
+  c3::HeadTailArgs a{};
+  a.x = x, a.wp = sp.wp, a.bias = bias, a.cin = 64, a.H = H, a.W = W;
+  a.tiles_x = (W + C3_GEO_TW[geo] - 1) / C3_GEO_TW[geo];
+  a.tiles_y = (H + C3_GEO_TH[geo] - 1) / C3_GEO_TH[geo];
+  a.ncb_all = 4, a.range_flag = range_flag_dev(), a.prep_flag = sp.flag, a.xbs = x_bstride;
+  const long ntiles = (long)B * a.tiles_x * a.tiles_y;
+  YS_CHECK_ARG(ntiles < (1L << 31), "conv3x3_head: too many tiles");
+  a.ntiles = (int)ntiles;
+  a.hw = hp.wp, a.hflag = hp.flag, a.hbias = head_bias;
+  a.hy = y + a_off, a.hbs = (long)(4 + nc) * A, a.A = A, a.nc = nc, a.stride = stride;
+  const long grid = persistent_grid(2L * cu_count(), ntiles);  // two workgroups per CU
+  using KH = void (*)(c3::HeadTailArgs);
+  static const KH kh[3][2] = {{c3::conv3x3_head_kernel<0, 1>, c3::conv3x3_head_kernel<0, 2>},
+                              {c3::conv3x3_head_kernel<1, 1>, c3::conv3x3_head_kernel<1, 2>},
+                              {c3::conv3x3_head_kernel<2, 1>, c3::conv3x3_head_kernel<2, 2>}};
+  hipLaunchKernelGGL(kh[geo][mode - 1], dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
+  YS_CHECK_LAUNCH("conv3x3_head");
+  return 0;
 }
 
 // ---- the fused Bottleneck (32 -> 32 -> 32) -------------------------------------------------------------------------

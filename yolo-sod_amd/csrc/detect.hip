@@ -11,7 +11,8 @@
 //                              ops.nms (CPU kernel: stable descending score sort, strict IoU > thr, area w/o +1).
 //
 // Class-wise NMS lives in nms.hip.
-#include "common.h"
+#include "split_conv.h"
+#include "detect_head_math.h"
 #include <math.h>
 #include <stdlib.h>
 
@@ -271,7 +272,7 @@ __global__ __launch_bounds__(256, C3 > 64 ? 2 : 3) void detect_head_x2_kernel(He
   static_assert(C2 == 64 && C3 % 32 == 0, "k steps of 32 channels");
   constexpr int NBW = C2 * 64, NCW = C3 * 16;  // image elements (box: 4 t x 2 s x 4 g x 16 rows x 8; cls: C3/32 s x ...)
   __shared__ __attribute__((aligned(16))) h16_t wl[2][NBW + NCW];
-  constexpr float WS = 64.0f;
+  constexpr float WS = headm::WS;
   const int b = blockIdx.y;
   int l = 0;
 #pragma unroll
@@ -368,70 +369,25 @@ __global__ __launch_bounds__(256, C3 > 64 ? 2 : 3) void detect_head_x2_kernel(He
     if (p0 >= HW) return;  // wave-uniform
     const int p = p0 + j;
     const bool ok = p < HW;
-    f32x4 acc[5];
+    // the arithmetic is detect_head_math.h's (one text with the tower conv's fused tail, conv3x3.hip)
+    f32x4 acc[4], accc[1];
 #pragma unroll
-    for (int t = 0; t < 5; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int s = 0; s < C2 / 32; ++s) {
-      f16x8_t fh, fl;
-      const f32x4 va{cb[8 * s], cb[8 * s + 1], cb[8 * s + 2], cb[8 * s + 3]};
-      const f32x4 vb2{cb[8 * s + 4], cb[8 * s + 5], cb[8 * s + 6], cb[8 * s + 7]};
-      split8x(va, vb2, fh, fl);  // loaded features: the 3-VALU split (common.h split2x)
-      rng = range_acc(range_acc(rng, va), vb2);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const int o = (t * 2 + s) * 512;
-        acc[t] = mfma_f16x3(*reinterpret_cast<const f16x8_t*>(wbh + o), *reinterpret_cast<const f16x8_t*>(wbl + o),
-                            fh, fl, acc[t]);
-      }
-    }
-#pragma unroll
-    for (int s = 0; s < C3 / 32; ++s) {
-      f16x8_t fh, fl;
-      const f32x4 va{cc[8 * s], cc[8 * s + 1], cc[8 * s + 2], cc[8 * s + 3]};
-      const f32x4 vb2{cc[8 * s + 4], cc[8 * s + 5], cc[8 * s + 6], cc[8 * s + 7]};
-      split8x(va, vb2, fh, fl);  // loaded features: the 3-VALU split (common.h split2x)
-      rng = range_acc(range_acc(rng, va), vb2);
-      const int o = NBW + s * 512;
-      acc[4] = mfma_f16x3(*reinterpret_cast<const f16x8_t*>(wbh + o), *reinterpret_cast<const f16x8_t*>(wbl + o), fh,
-                          fl, acc[4]);
-    }
-    // DFL (block.py:79-82)
+    for (int t = 0; t < 4; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+    accc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+    headm::mma<4, C2 / 32>(
+        cb, [&](int idx, int pl) { return *reinterpret_cast<const f16x8_t*>((pl ? wbl : wbh) + idx * 512); }, acc, rng);
+    headm::mma<1, C3 / 32>(
+        cc, [&](int idx, int pl) { return *reinterpret_cast<const f16x8_t*>((pl ? wbl : wbh) + NBW + idx * 512); },
+        accc, rng);
     float dist[4];
-#pragma unroll
-    for (int s = 0; s < 4; ++s) {
-      float v[4];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = acc[s][r] * (1.0f / WS) + bbr[s][r];
-      float mx = fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3]));
-      mx = xor32_max(xor16_max(mx));
-      float sum = 0.f, e = 0.f;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        v[r] = __expf(v[r] - mx);
-        sum += v[r];
-        e += (float)(4 * g + r) * v[r];
-      }
-      sum = xor32_sum(xor16_sum(sum));
-      e = xor32_sum(xor16_sum(e));
-      dist[s] = e * __builtin_amdgcn_rcpf(sum);
-    }
+    headm::dfl(acc, bbr, g, dist);
     if (!ok) return;
     const int iy = p / W, ix = p - iy * W;
-    const float ax = (float)ix + 0.5f, ay = (float)iy + 0.5f;
-    const float x1 = ax - dist[0], y1 = ay - dist[1];
-    const float x2 = ax + dist[2], y2 = ay + dist[3];
-    const float out = g == 0 ? ((x1 + x2) / 2.0f) * st
-                    : g == 1 ? ((y1 + y2) / 2.0f) * st
-                    : g == 2 ? (x2 - x1) * st
-                             : (y2 - y1) * st;
-    yb[(long)g * d.A + p] = out;
+    yb[(long)g * d.A + p] = headm::box_out(dist, ix, iy, st, g);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int c = 4 * g + r;
-      // class score: sigmoid on the hardware exp2 / rcp (1-2 ulp; the libm expf + IEEE division were ~15 % of the
-      // kernel's VALU, and the split products already carry a few ulp)
-      if (c < nc) yb[(long)(4 + c) * d.A + p] = sigmoid_fast_(acc[4][r] * (1.0f / WS) + bcr[r]);
+      if (c < nc) yb[(long)(4 + c) * d.A + p] = headm::cls_out(accc[0][r], bcr[r]);
     }
   };
   static_assert(NTS % 2 == 0, "group pairs");
@@ -451,9 +407,50 @@ __global__ __launch_bounds__(256, C3 > 64 ? 2 : 3) void detect_head_x2_kernel(He
   range_report(d.range_flag, rng);
 }
 
+// The weight planes of one tower's last 1x1 conv, W [rows][64], written once per parameter version for the tower conv
+// that runs the head's tail in its epilogue (conv3x3.hip, conv3x3_head_kernel): the hi plane then the lo plane,
+// [t][s][g][row][i] each, bit for bit what detect_head_x2_kernel splits per workgroup (rows past `rows` zero).
+// One thread per pair of k slots.
+__global__ __launch_bounds__(256) void detect_head_prep_kernel(const float* __restrict__ w, int rows, int ntile,
+                                                              h16_t* __restrict__ wp, unsigned* range_flag,
+                                                              unsigned* prep_flag) {
+  const int u = blockIdx.x * 256 + threadIdx.x;
+  if (u >= ntile * 512) return;
+  const f32x2 v = headm::weight_pair(w, rows, 2 * u);
+  uint32_t h, lo;
+  split2(v, h, lo);
+  reinterpret_cast<uint32_t*>(wp)[u] = h;
+  reinterpret_cast<uint32_t*>(wp + ntile * 1024)[u] = lo;
+  const float m = range_acc2(0.f, v);
+  range_report(range_flag, m);
+  range_report(prep_flag, m);
+}
+
 }  // namespace ys
 
 using namespace ys;
+
+// Prepared block of a tower's last 1x1 conv W [rows][64] (rows 64: the box conv; 1 .. 16: the class conv, padded to
+// one 16-row tile): 2 x ntile x 1024 fp16 values and the block's own range word (split_conv.h's block layout).
+static int head_prep_tiles(int rows) { return rows == 64 ? 4 : (rows >= 1 && rows <= 16 ? 1 : 0); }
+YS_EXPORT size_t yolosod_detect_head_prep_bytes(int rows) {
+  const int nt = head_prep_tiles(rows);
+  return nt ? split_prep_bytes((size_t)2 * nt * 1024) : 0;
+}
+YS_EXPORT int yolosod_detect_head_prepare(const float* w, int rows, void* prep, size_t prep_bytes, void* stream) {
+  const int nt = head_prep_tiles(rows);
+  YS_CHECK_ARG(nt > 0, "detect_head_prepare: rows=%d unsupported (64, or 1..16)", rows);
+  YS_CHECK_ARG(w && prep, "detect_head_prepare: null pointer");
+  SplitPrep sp;
+  YS_CHECK_ARG(split_prep_carve(prep, prep_bytes, (size_t)2 * nt * 1024, &sp),
+               "detect_head_prepare: block too small (%zu)", prep_bytes);
+  hipStream_t st = (hipStream_t)stream;
+  YS_CHECK_ARG(hipMemsetAsync(sp.flag, 0, sizeof(unsigned), st) == hipSuccess, "detect_head_prepare: flag reset failed");
+  hipLaunchKernelGGL(detect_head_prep_kernel, dim3((unsigned)(nt * 2)), dim3(256), 0, st, w, rows, nt, sp.wp,
+                     range_flag_dev(), sp.flag);
+  YS_CHECK_LAUNCH("detect_head_prepare");
+  return 0;
+}
 
 YS_EXPORT int yolosod_detect_decode(int nl, const float* const* maps, const int* heights, const int* widths,
                                     const float* strides, int B, int nc, int reg_max, float* y, void* stream) {

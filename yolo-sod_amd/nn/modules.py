@@ -231,6 +231,13 @@ def _onoff_switch(name: str, value: str) -> bool:
 # taken when both convs are on the stride-1 fp16-split kernel and the library says the map is large enough for the
 # launch to pay (yolosod_debug_bottleneck3x3_fused). YOLOSOD_BOTTLENECK_FUSE=0: always the two launches
 BOTTLENECK_FUSE = _onoff_switch("YOLOSOD_BOTTLENECK_FUSE", os.environ.get("YOLOSOD_BOTTLENECK_FUSE", "1"))
+# the Detect towers' last 3x3 convs (64 -> 64) with the tower's 1x1 conv and the decode in their epilogue
+# (csrc/conv3x3.hip, conv3x3_head_kernel), bit-identical to the conv launches followed by the head kernel, on the levels
+# the library names (yolosod_debug_conv3x3_head_fused: maps large enough for 64-channel groups; P2 / P3 at the bench's
+# batch): their [B, 64, H, W] tower maps are never written. fp32, c2 == c3 == 64, the fp16-split kernels on (not inside
+# _hip.exact_fp32_matrix()). YOLOSOD_HEAD_FUSE=0: the conv launches and the head kernel on every level
+HEAD_FUSE_DEFAULT = "1"
+HEAD_FUSE = _onoff_switch("YOLOSOD_HEAD_FUSE", os.environ.get("YOLOSOD_HEAD_FUSE", HEAD_FUSE_DEFAULT))
 
 
 def _s2_on(s2, layer=None):
@@ -964,6 +971,68 @@ class Detect(nn.Module):
         """Level i's box / class tower features (cv2[i][:-1], cv3[i][:-1]): the inputs of the fused head kernel."""
         return self.cv2[i][:-1](xi).contiguous(), self.cv3[i][:-1](xi).contiguous()
 
+    def head_fuse_level(self, i, xi) -> bool:
+        """Whether level i's towers run their last conv, 1x1 conv and decode as one launch on the input map ``xi``
+        (HEAD_FUSE; ``tower_into``). False on every level gives the head kernel, launch for launch as without the
+        switch."""
+        if not (HEAD_FUSE and CONV3X3 != "0" and xi.dtype == torch.float32 and self._fused_ok([xi])
+                and _hip.split_convs_enabled()):
+            return False
+        B, _, H, W = xi.shape
+        if W % 4 or not _hip.conv3x3_head_fused(B, H, W):
+            return False
+        for seq in (self.cv2[i], self.cv3[i]):
+            if not (len(seq) == 3 and isinstance(seq[1], Conv) and seq[1].is_fused() and seq[1].tower):
+                return False
+            cv, last = seq[1].conv, seq[2]
+            if not (isinstance(seq[1].act, nn.SiLU) and cv.bias is not None and cv.in_channels == 64
+                    and cv.out_channels == 64 and cv.kernel_size == (3, 3) and cv.stride == (1, 1)
+                    and cv.padding == (1, 1) and cv.dilation == (1, 1) and cv.groups == 1
+                    and last.in_channels == 64 and last.kernel_size == (1, 1) and last.bias is not None):
+                return False
+        return True
+
+    def head_fuse_levels(self, x):
+        return tuple(self.head_fuse_level(i, xi) for i, xi in enumerate(x))
+
+    def tower_into(self, y, i, mode, xi, a_off):
+        """Level i's box (``mode`` 1: cv2[i]) or class (2: cv3[i]) tower on ``xi``, decoded into its rows of anchors
+        [a_off, a_off + H W) of y [B, 4 + nc, A]: the first conv as ever, then the last conv + 1x1 conv + decode in one
+        launch (_hip.conv3x3_head). The caller has asked head_fuse_levels."""
+        seq = (self.cv2 if mode == 1 else self.cv3)[i]
+        f = seq[0](xi)
+        conv, last = seq[1].conv, seq[2]
+        rows = 64 if mode == 1 else self.nc
+        prep = _prep(conv, "c3prep", _hip.conv3x3_prepare)
+        hprep = lambda: _cached(last, "headprep", (last.weight,),  # noqa: E731
+                                lambda: _hip.detect_head_prepare(last.weight, rows))
+        (hb,) = _f32(last, "headbias", last.bias)
+        return _hip.conv3x3_head(f, conv.bias, prep, hprep, hb, mode, self.nc, float(self.stride[i]), y, a_off)
+
+    def forward_levels(self, y, feats, inputs):
+        """The head kernel on the levels that have tower features (``feats[i]`` a (box, class) pair), into y; the
+        others (``feats[i]`` None) were decoded by their towers (``tower_into``) from ``inputs[i]``. One launch per run
+        of consecutive levels."""
+        nl = self.nl
+        p = _f32(self, "head", *[c[-1].weight for c in self.cv2], *[c[-1].bias for c in self.cv2],
+                 *[c[-1].weight for c in self.cv3], *[c[-1].bias for c in self.cv3])
+        w = lambda t: t.reshape(t.shape[0], -1)  # noqa: E731
+        fb = [f[0] if f is not None else tuple(inputs[i].shape[2:]) for i, f in enumerate(feats)]
+        fc = [f[1] if f is not None else None for f in feats]
+        args = (fb, fc, [w(t) for t in p[:nl]], list(p[nl:2 * nl]), [w(t) for t in p[2 * nl:3 * nl]],
+                list(p[3 * nl:]), [float(s) for s in self.stride], self.nc, self.reg_max)
+        l0 = 0
+        while l0 < nl:
+            if feats[l0] is None:
+                l0 += 1
+                continue
+            l1 = l0
+            while l1 < nl and feats[l1] is not None:
+                l1 += 1
+            _hip.detect_head_into(y, l0, l1, *args)
+            l0 = l1
+        return y, RawMaps(self, fb, fc, inputs)
+
     def forward_towers(self, feats, wait_last=None):
         """The fused head on tower features computed elsewhere (the executor's side streams): [(fb_i, fc_i)].
         ``wait_last``: the levels before the last are decoded first, then ``wait_last()`` (the caller's stream
@@ -974,6 +1043,20 @@ class Detect(nn.Module):
     def _fused_forward(self, x):
         """cv2[i][:-1] / cv3[i][:-1] towers (PyTorch-ROCm convs + HIP epilogues), then the last 1x1 convs of both
         towers fused with DFL / dist2bbox / sigmoid in one HIP kernel (head.py:70 + _inference :100-131)."""
+        fuse = self.head_fuse_levels(x)
+        if any(fuse):
+            A = sum(t.shape[2] * t.shape[3] for t in x)
+            y = torch.empty((x[0].shape[0], 4 + self.nc, A), dtype=torch.float32, device=x[0].device)
+            feats, a_off = [], 0
+            for i in range(self.nl):
+                if fuse[i]:
+                    self.tower_into(y, i, 1, x[i], a_off)
+                    self.tower_into(y, i, 2, x[i], a_off)
+                    feats.append(None)
+                else:
+                    feats.append(self.tower_features(i, x[i]))
+                a_off += x[i].shape[2] * x[i].shape[3]
+            return self.forward_levels(y, feats, list(x))
         fb, fc = [], []
         for i in range(self.nl):
             b, c = self.tower_features(i, x[i])
@@ -1039,14 +1122,26 @@ class RawMaps(Sequence):
     (head.py:70-74), computed from the kept tower features on first access (``raw_from_features``) - the fused
     kernel never writes them, and callers that only read ``preds[0]`` (NMS, ops.py:219-220) never pay for them.
     Indexing / iteration / ``len`` / ``list(...)`` give the reference's tensors; ``features`` holds the
-    (box, class) tower features per level; ``materialize()`` returns the plain list."""
+    (box, class) tower features per level; ``materialize()`` returns the plain list. A level whose towers decoded it
+    themselves (Detect.tower_into) has no stored features: its input map is kept instead (``inputs``), and its
+    features are computed through ``tower_features`` on first access."""
 
-    __slots__ = ("_det", "features", "_maps")
+    __slots__ = ("_det", "_feats", "_inputs", "_maps")
 
-    def __init__(self, det, fb, fc):
+    def __init__(self, det, fb, fc, inputs=None):
         self._det = det
-        self.features = list(zip(fb, fc))
+        self._feats = [(b, c) if isinstance(b, torch.Tensor) else None for b, c in zip(fb, fc)]
+        self._inputs = inputs
         self._maps = None
+
+    @property
+    def features(self):
+        for i, f in enumerate(self._feats):
+            if f is None:
+                xi = self._inputs[i]
+                with torch.inference_mode(True) if xi.is_inference() else contextlib.nullcontext():
+                    self._feats[i] = self._det.tower_features(i, xi)
+        return self._feats
 
     def materialize(self) -> list:
         if self._maps is None:
@@ -1062,7 +1157,7 @@ class RawMaps(Sequence):
         return self.materialize()[i]
 
     def __len__(self):
-        return len(self.features)
+        return len(self._feats)
 
     def __iter__(self):
         return iter(self.materialize())

@@ -271,6 +271,7 @@ class BaseModel(nn.Module):
         plan = self._concat_producers()
         det = self.model[-1]
         towers = lvl = main = side = None
+        img_hw = tuple(x.shape[2:])
         streams = STREAMS
         if _STREAMS_ENV is None and x.dtype == torch.bfloat16:
             streams = 2
@@ -286,6 +287,10 @@ class BaseModel(nn.Module):
             if side is None or len(side) != SIDE_STREAMS or side[0].device != x.device:
                 side = self._side_streams = [torch.cuda.Stream(device=x.device) for _ in range(SIDE_STREAMS)]
             rr = 0  # next side stream (round robin over towers)
+            head_y = None  # the prediction tensor, once a level's towers decode into it themselves (M.HEAD_FUSE)
+            lvl_in = {}  # level -> its input map
+            # every level's map size, known before the maps exist: y is laid out when the first fused tower starts
+            head_hw = [_level_hw(img_hw, float(s)) for s in det.stride]
         y = []
         pend = {}  # concat index -> (buffer, channel offset of each input)
         cvpend = {}  # concat index -> (part 0 is an Upsample's source,): handed to the next C2f as a CatView
@@ -378,7 +383,15 @@ class BaseModel(nn.Module):
                 feats = [towers[k] for k in range(det.nl)]
                 for sd in side:  # every level's tower features are ready (and owned by main from here)
                     main.wait_stream(sd)
-                x = det.forward_towers(feats)
+                if head_y is None:
+                    x = det.forward_towers(feats)
+                else:  # the head kernel on the levels that still have tower features
+                    ins = [lvl_in[k] for k in range(det.nl)]
+                    if [tuple(t.shape[2:]) for t in ins] == head_hw:
+                        x = det.forward_levels(head_y, feats, ins)
+                    else:  # a level's size is not what the strides gave: y's layout was wrong, every level afresh
+                        x = det.forward_towers([f if f is not None else det.tower_features(k, ins[k])
+                                                for k, f in enumerate(feats)])
             else:
                 x = m(inp)
             if towers is not None and m is not det:
@@ -388,6 +401,27 @@ class BaseModel(nn.Module):
                     ready.append((lvl[m.i], x))
                 if ready and (streams != 2 or m.i >= last_mafn):
                     for k, xk in ready:
+                        lvl_in[k] = xk
+                        if (None not in head_hw and tuple(xk.shape[2:]) == head_hw[k]
+                                and det.head_fuse_level(k, xk)):
+                            # this level's towers decode it themselves: first conv, then last conv + 1x1 conv + decode
+                            # in one launch into y, which is allocated on the main stream before the first tower
+                            # (the other levels' maps do not exist yet: their sizes follow from the image's by
+                            # the strides; should a map turn out otherwise, the Detect layer below redoes the level)
+                            if head_y is None:
+                                head_off = [sum(h * w for h, w in head_hw[:j]) for j in range(det.nl + 1)]
+                                head_y = torch.empty((xk.shape[0], 4 + det.nc, head_off[-1]), dtype=torch.float32,
+                                                     device=xk.device)
+                            for mode in (1, 2):
+                                sd = side[rr % len(side)]
+                                rr += 1
+                                sd.wait_stream(main)
+                                xk.record_stream(sd)
+                                head_y.record_stream(sd)
+                                with torch.cuda.stream(sd):
+                                    det.tower_into(head_y, k, mode, xk, head_off[k])
+                            towers[k] = None
+                            continue
                         feats = []
                         for tower in (det.cv2[k], det.cv3[k]):  # box, class tower (Detect.tower_features)
                             sd = side[rr % len(side)]
@@ -419,6 +453,18 @@ class BaseModel(nn.Module):
         self._fused = True
         self._cplan = None
         return self
+
+
+def _level_hw(img_hw, stride):
+    """The map size of a Detect level at ``stride`` (a power of two) for an image of ``img_hw``: every stride-2 stage
+    of the model is a 3x3 / pad 1 conv, which halves a size rounding up. None for any other stride."""
+    h, w = img_hw
+    n = int(round(math.log2(stride))) if stride >= 1 else -1
+    if n < 0 or 2.0 ** n != stride:
+        return None
+    for _ in range(n):
+        h, w = (h + 1) // 2, (w + 1) // 2
+    return h, w
 
 
 def _fuse_conv_and_bn(conv: nn.Conv2d, bn: nn.BatchNorm2d) -> nn.Conv2d:
