@@ -241,7 +241,23 @@ int yolosod_tta_views(const void* x, int B, int C, int H, int W, int bf16, const
                       int max_pw, void* stream);
 int yolosod_tta_merge(const float* y, int B, int nc, int A, int src_lo, int n, float* cat, int A_tot, int dst,
                       float scale, int flip, float img_w, float img_h, void* stream);
-/* BaseValidator.match_predictions over box_iou   ultralytics/engine/validator.py:222-262 (greedy path),
+/* Sliced inference with test-time augmentation (the project's own; csrc/tile_merge_tta.hip): one branch of one model
+ * call straight into the per-frame prediction tensor, one launch, no concatenated tensor in between. y: [n][4+nc][A]
+ * fp32, the head's output for view (scale, flip) of n tiles, in that view's canvas pixels; its anchors [src_lo,
+ * src_lo + n_k) go to anchors [slot*A_tot + dst, + n_k) of merged [F][4+nc][S*A_tot] (fp32, frame pixels). desc: device
+ * int32 [rows][16], yolosod_tile_merge's descriptor unchanged; (img_w, img_h) the tiles' canvas. Per anchor, fp32, IEEE
+ * division, every operation rounded on its own: x, y, w, h each / scale, then x = img_w - x (flip 3) or y = img_h - y
+ * (flip 2) (yolosod_tta_merge's arithmetic); on that, (xy - pad) / gain, wh / gain, the cut test against cut_margin on
+ * interior edges, + off, scores zeroed where cut (yolosod_tile_merge's). Bit-identical to yolosod_tta_merge into
+ * cat [n][4+nc][A_tot] followed by yolosod_tile_merge of cat with A = A_tot. A src = -1 row writes zeros to the
+ * branch's range of its slot; over the launches of all branches of one model call every element of every named slot is
+ * written exactly once, nothing else is touched, no atomics: deterministic. A row naming a src >= n, a frame outside
+ * [0, F) or a slot outside [0, S) writes nothing. nc in 1..64, S*A_tot*nc < 2^32, rows in 1..65535, scale finite and
+ * > 0, flip 0 / 2 / 3, the ranges inside y and a slot; 4-byte accesses (A_tot is odd at the workload's shapes). */
+int yolosod_tile_merge_tta(const float* y, int n, int nc, int A, int src_lo, int n_k, const int32_t* desc, int rows,
+                           float* merged, int F, int S, int A_tot, int dst, float scale, int flip, float img_w,
+                           float img_h, float cut_margin, void* stream);
+/* BaseValidator.match_predictions over box_iou  ultralytics/engine/validator.py:222-262 (greedy path),
  * ultralytics/utils/metrics.py:52-71, for a whole batch of padded NMS rows in one launch, no host sync
  * (csrc/eval_match.hip). det: [B][D][6] padded NMS rows (x1, y1, x2, y2, conf, cls), counts: device [B]. labels:
  * device [L][5] = cls, x1, y1, x2, y2, the images' labels back to back (may be null when there are none); label_off:

@@ -56,6 +56,7 @@ SIGNATURES = {
     "yolosod_letterbox_ingest": (_i, [_vp, _i, _vp, _l, _i, _i, _i, _i, _vp]),
     "yolosod_scale_boxes": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "yolosod_tile_merge": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _f, _vp]),
+    "yolosod_tile_merge_tta": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp]),
     "yolosod_match_predictions": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "yolosod_tta_views": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "yolosod_tta_merge": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _i, _f, _f, _vp]),
@@ -1338,7 +1339,6 @@ def tile_merge(y, rows, merged, A, cut_margin=None):
 
     The descriptor is built here and goes up as one pinned non-blocking copy; everything the kernel relies on is
     checked here first: nothing is launched on arguments that fail."""
-    import numpy as np
     lib = load_library()
     for t, name in ((y, "y"), (merged, "merged")):
         if not isinstance(t, torch.Tensor):
@@ -1366,39 +1366,115 @@ def tile_merge(y, rows, merged, A, cut_margin=None):
     S = SA // A
     if S * A * nc >= 1 << 32:
         raise RuntimeError(f"tile_merge: S * A * nc = {S} * {A} * {nc} >= 2^32")
-    rows = list(rows)
-    if not 1 <= len(rows) <= 65535:
-        raise RuntimeError(f"tile_merge: {len(rows)} descriptor rows (1..65535)")
-    desc = np.zeros((len(rows), 16), dtype=np.int32)
-    fl = desc.view(np.float32)
-    named = set()
-    for i, r in enumerate(rows):
-        if len(r) != 11 or len(r[10]) != 4:
-            raise RuntimeError(f"tile_merge: row {i}: expected (src, frame, slot, gain, pad_x, pad_y, off_x, off_y, "
-                               "tile_w, tile_h, (left, right, top, bottom))")
-        src, frame, slot = int(r[0]), int(r[1]), int(r[2])
-        if not -1 <= src < n:
-            raise RuntimeError(f"tile_merge: row {i}: src {src} outside [-1, {n})")
-        if not 0 <= frame < F:
-            raise RuntimeError(f"tile_merge: row {i}: frame {frame} outside [0, {F})")
-        if not 0 <= slot < S:
-            raise RuntimeError(f"tile_merge: row {i}: slot {slot} outside [0, {S})")
-        if (frame, slot) in named:
-            raise RuntimeError(f"tile_merge: row {i}: slot {slot} of frame {frame} is named twice")
-        named.add((frame, slot))
-        gain = float(r[3])
-        if src >= 0 and not (gain > 0.0 and gain < float("inf")):
-            raise RuntimeError(f"tile_merge: row {i}: gain {gain}")
-        desc[i, :3] = (src, frame, slot)
-        desc[i, 3] = sum(1 << k for k in range(4) if r[10][k])
-        fl[i, 4:11] = [float(v) for v in r[3:10]]
+    desc = _tile_merge_desc("tile_merge", rows, n, F, S)
     cm = -1.0 if cut_margin is None else float(cut_margin)
     if cm != cm:
         raise RuntimeError("tile_merge: cut_margin is NaN")
     dev = y.device
     d = torch.from_numpy(desc).pin_memory().to(dev, non_blocking=True)
     _check(_launch(("tile_merge", (n, no, A), (F, S)), dev, lib.yolosod_tile_merge, y.data_ptr(), n, nc, A,
-                   d.data_ptr(), len(rows), merged.data_ptr(), F, S, cm, _stream(dev)), "tile_merge")
+                   d.data_ptr(), len(desc), merged.data_ptr(), F, S, cm, _stream(dev)), "tile_merge")
+    return merged
+
+
+def _tile_merge_desc(who, rows, n, F, S):
+    """The int32 [rows, 16] descriptor of ``tile_merge`` / ``tile_merge_tta`` from ``SlicePlan.merge_rows``' tuples, on
+    the host; refuses a row that names something outside y [n, ...] or merged [F, ., S * .], or a slot twice."""
+    import numpy as np
+    rows = list(rows)
+    if not 1 <= len(rows) <= 65535:
+        raise RuntimeError(f"{who}: {len(rows)} descriptor rows (1..65535)")
+    desc = np.zeros((len(rows), 16), dtype=np.int32)
+    fl = desc.view(np.float32)
+    named = set()
+    for i, r in enumerate(rows):
+        if len(r) != 11 or len(r[10]) != 4:
+            raise RuntimeError(f"{who}: row {i}: expected (src, frame, slot, gain, pad_x, pad_y, off_x, off_y, "
+                               "tile_w, tile_h, (left, right, top, bottom))")
+        src, frame, slot = int(r[0]), int(r[1]), int(r[2])
+        if not -1 <= src < n:
+            raise RuntimeError(f"{who}: row {i}: src {src} outside [-1, {n})")
+        if not 0 <= frame < F:
+            raise RuntimeError(f"{who}: row {i}: frame {frame} outside [0, {F})")
+        if not 0 <= slot < S:
+            raise RuntimeError(f"{who}: row {i}: slot {slot} outside [0, {S})")
+        if (frame, slot) in named:
+            raise RuntimeError(f"{who}: row {i}: slot {slot} of frame {frame} is named twice")
+        named.add((frame, slot))
+        gain = float(r[3])
+        if src >= 0 and not (gain > 0.0 and gain < float("inf")):
+            raise RuntimeError(f"{who}: row {i}: gain {gain}")
+        desc[i, :3] = (src, frame, slot)
+        desc[i, 3] = sum(1 << k for k in range(4) if r[10][k])
+        fl[i, 4:11] = [float(v) for v in r[3:10]]
+    return desc
+
+
+def tile_merge_tta(y, rows, merged, A_tot, branch, canvas_hw, cut_margin=None):
+    """One branch of one augmented model call on tiles straight into the per-frame prediction tensors, one launch
+    (yolosod_tile_merge_tta): ``y`` [n, 4+nc, A_k] fp32 is the Detect output of view ``branch`` of n tiles, in that
+    view's canvas pixels; ``merged`` [F, 4+nc, S*A_tot] fp32 the batch's NMS input in frame pixels. ``branch`` is a
+    ``data.tta.TTABranch`` or its five terms ``(src_lo, n, dst, scale, flip)``: anchors [src_lo, src_lo + n) of y go
+    to anchors [slot*A_tot + dst, + n) of every slot that ``rows`` names (``SlicePlan.merge_rows``, as ``tile_merge``
+    takes them; a ``src = -1`` row: zeros). ``canvas_hw`` = (h, w) of the tiles' canvas, what a flip mirrors in.
+    Per anchor ``tta_merge``'s arithmetic, then ``tile_merge``'s on its result: bit for bit ``tta_merge`` into a
+    concatenated tensor followed by ``tile_merge`` of it with A = A_tot, without that tensor. The K launches of one
+    model call write every element of the named slots exactly once. Returns ``merged``.
+
+    The descriptor is built here and goes up as one pinned non-blocking copy; everything the kernel relies on is
+    checked here first: nothing is launched on arguments that fail. No host sync."""
+    lib = load_library()
+    for t, name in ((y, "y"), (merged, "merged")):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"tile_merge_tta: {name}: expected a tensor")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"tile_merge_tta: {name}: HIP kernel requires a GPU tensor (got device {t.device}); "
+                               "no CPU fallback")
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"tile_merge_tta: {name}: expected float32, got {t.dtype}")
+        if t.dim() != 3:
+            raise RuntimeError(f"tile_merge_tta: {name}: expected 3 dimensions, got shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"tile_merge_tta: {name}: expected a contiguous tensor")
+    if merged.device != y.device:
+        raise RuntimeError(f"tile_merge_tta: y on {y.device}, merged on {merged.device}")
+    n, no, A = (int(v) for v in y.shape)
+    nc, A_tot = no - 4, int(A_tot)
+    if n < 1 or A < 1 or not 1 <= nc <= TILE_MERGE_MAX_NC:
+        raise RuntimeError(f"tile_merge_tta: y {tuple(y.shape)} unsupported (n >= 1, 1..{TILE_MERGE_MAX_NC} classes)")
+    if A * no >= 1 << 31:
+        raise RuntimeError("tile_merge_tta: A * (4 + nc) >= 2^31")
+    F, SA = int(merged.shape[0]), int(merged.shape[2])
+    if A_tot < 1 or F < 1 or int(merged.shape[1]) != no or SA < A_tot or SA % A_tot:
+        raise RuntimeError(f"tile_merge_tta: merged {tuple(merged.shape)} is not [F, {no}, S * {A_tot}]")
+    S = SA // A_tot
+    if S * A_tot * nc >= 1 << 32:
+        raise RuntimeError(f"tile_merge_tta: S * A_tot * nc = {S} * {A_tot} * {nc} >= 2^32")
+    if hasattr(branch, "src_lo"):
+        if int(branch.A) != A:
+            raise RuntimeError(f"tile_merge_tta: y has {A} anchors, the branch {int(branch.A)}")
+        branch = (branch.src_lo, branch.n, branch.dst, branch.scale, branch.flip)
+    if len(branch) != 5:
+        raise RuntimeError("tile_merge_tta: branch: expected a TTABranch or (src_lo, n, dst, scale, flip)")
+    src_lo, n_k, dst, scale, flip = int(branch[0]), int(branch[1]), int(branch[2]), float(branch[3]), branch[4]
+    if n_k < 1 or src_lo < 0 or src_lo + n_k > A:
+        raise RuntimeError(f"tile_merge_tta: source anchors [{src_lo}, {src_lo + n_k}) leave y's {A}")
+    if dst < 0 or dst + n_k > A_tot:
+        raise RuntimeError(f"tile_merge_tta: destination anchors [{dst}, {dst + n_k}) leave a slot's {A_tot}")
+    if not (scale > 0.0 and scale < float("inf")):
+        raise RuntimeError(f"tile_merge_tta: scale {scale} (finite and > 0 expected)")
+    if flip not in TTA_FLIPS:
+        raise RuntimeError(f"tile_merge_tta: flip {flip} (None, 2 or 3)")
+    img_h, img_w = int(canvas_hw[0]), int(canvas_hw[1])
+    desc = _tile_merge_desc("tile_merge_tta", rows, n, F, S)
+    cm = -1.0 if cut_margin is None else float(cut_margin)
+    if cm != cm:
+        raise RuntimeError("tile_merge_tta: cut_margin is NaN")
+    dev = y.device
+    d = torch.from_numpy(desc).pin_memory().to(dev, non_blocking=True)
+    _check(_launch(("tile_merge_tta", (n, no, n_k), (F, S, A_tot)), dev, lib.yolosod_tile_merge_tta, y.data_ptr(), n,
+                   nc, A, src_lo, n_k, d.data_ptr(), len(desc), merged.data_ptr(), F, S, A_tot, dst, scale,
+                   TTA_FLIPS[flip], float(img_w), float(img_h), cm, _stream(dev)), "tile_merge_tta")
     return merged
 
 

@@ -22,7 +22,9 @@ ARCH = os.environ.get("YOLOSOD_ARCH", "gfx950")
 EXTRA = {"detect.hip": ["-ffp-contract=off"], "nms.hip": ["-ffp-contract=off"],
          "tile_merge.hip": ["-ffp-contract=off"], "eval_match.hip": ["-ffp-contract=off"],
          # the augmented views' bilinear blend and the branch merge: every product and sum rounds on its own
-         "tta.hip": ["-ffp-contract=off"]}
+         "tta.hip": ["-ffp-contract=off"],
+         # both of the above in one pass: bit-identical to the two launches only if nothing is contracted here either
+         "tile_merge_tta.hip": ["-ffp-contract=off"]}
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-variable",
           "-Wno-unused-function", f"-I{INCLUDE}", f"-I{CSRC}"]
 

@@ -210,15 +210,27 @@ class SlicedPredictor:
     (``_hip.tile_merge`` per call into merged [F, 4+nc, S*A], frame pixels) -> :meth:`postprocess` (NMS on merged,
     clip to the frame). ``index`` of a detection is ``slot * A + anchor``; ``plan.slot(frame, slot)`` is its tile.
 
-    Test-time augmentation (``DetectionPredictor(augment=True)``) is out of scope here: the tiles are run at one scale.
+    ``augment=True``: test-time augmentation on every tile (``scales`` / ``flips`` as ``DetectionModel.tta_plan`` takes
+    them; None: the reference's three views). Every tile is letterboxed onto the same ``imgsz`` canvas, so one
+    ``TTAPlan`` serves the batch; a model call is then K branches, :meth:`forward_tiles` gives per call the tuple of
+    their outputs [n_i, 4+nc, A_k] (each in its own view's pixels), and :meth:`merge` puts every branch straight into
+    merged [F, 4+nc, S*A_tot] with one ``_hip.tile_merge_tta`` launch: the concatenated tensor of
+    ``model(x, augment=True)`` is never made. ``index`` is then ``slot * A_tot + j``, j along the plan's
+    concatenation; :meth:`locate` takes it apart. Everything after ``merged`` is the same.
 
     ``cut_margin`` (tile pixels; None: off): a candidate whose box comes within it of a tile edge that is interior to
     the frame is dropped before NMS - the tile saw the object truncated, a neighbouring tile or the whole-frame slot
     sees it whole. ``merged`` takes F * (4+nc) * S * A * 4 bytes."""
 
     def __init__(self, model, slice=640, overlap=0.2, full_frame=True, cut_margin=None, batch=32, conf=0.25, iou=0.7,
-                 max_det=300, classes=None, agnostic_nms=False, multi_label=False, imgsz=640):
+                 max_det=300, classes=None, agnostic_nms=False, multi_label=False, imgsz=640, augment=False, scales=None,
+                 flips=None):
         self.model = model
+        self.augment = bool(augment)
+        if not self.augment and (scales is not None or flips is not None):
+            raise ValueError("SlicedPredictor: scales / flips are the views of augment=True")
+        self.scales = None if scales is None else tuple(scales)
+        self.flips = None if flips is None else tuple(flips)
         self.slice, self.overlap, self.full_frame = slice, overlap, bool(full_frame)
         self.cut_margin = None if cut_margin is None else float(cut_margin)
         self.batch = int(batch)
@@ -250,40 +262,82 @@ class SlicedPredictor:
         return _hip.letterbox_ingest(self._views(ts, plan, lo, hi), plan.canvas, geoms, self.dtype,
                                      pad_value=plan.pad_value)
 
+    def tta_plan(self, plan):
+        """The ``TTAPlan`` of the tiles of ``plan`` (``augment=True``): every tile is on the one canvas."""
+        if not self.augment:
+            raise RuntimeError("SlicedPredictor: tta_plan is for augment=True")
+        return self.model.tta_plan(plan.canvas, self.scales, self.flips)
+
+    def _calls(self, ts, plan):
+        """The model calls in ``plan.order``, one at a time: yields ``(lo, y)``, y the Detect output [n_i, 4+nc, A] of
+        tiles ``order[lo:lo + n_i]``, or with ``augment`` one branch of it, ``(lo, (k, y_k))``, K times per call."""
+        tp = self.tta_plan(plan) if self.augment else None
+        for lo, hi in plan.chunks(self.batch):
+            x = self.ingest_tiles(ts, plan, lo, hi)
+            if tp is None:
+                preds = self.model(x)
+                yield lo, preds[0] if isinstance(preds, (list, tuple)) else preds
+            else:
+                for k, y in self.model.augment_branches(x, tp):
+                    yield lo, (k, y)
+
     @torch.inference_mode()
     def forward_tiles(self, frames, plan):
         """The Detect outputs [n_i, 4+nc, A] (fp32, canvas pixels) of the model calls, ``batch`` tiles at most each, in
-        ``plan.order``. CPU frames go up once."""
+        ``plan.order``; with ``augment`` per call the tuple of its K branch outputs [n_i, 4+nc, A_k], each in its own
+        view's pixels (the views are ``_hip.tta_views`` of the ingested tiles). CPU frames go up once."""
         ts = frames_to_device(frames, self.device, "SlicedPredictor")
         if [tuple(t.shape[:2]) for t in ts] != plan.shapes:
             raise ValueError("SlicedPredictor: the plan was made for other frame shapes")
-        ys = []
-        for lo, hi in plan.chunks(self.batch):
-            preds = self.model(self.ingest_tiles(ts, plan, lo, hi))
-            ys.append(preds[0] if isinstance(preds, (list, tuple)) else preds)
+        ys = [y for _, y in self._calls(ts, plan)]
+        if self.augment:
+            K = len(self.tta_plan(plan))
+            ys = [tuple(y for _, y in ys[i:i + K]) for i in range(0, len(ys), K)]
         return ys
+
+    def _merge_into(self, merged, y, plan, lo):
+        """One call's output (with ``augment`` one branch of it, ``(k, y_k)``) for tiles ``order[lo:lo + n]`` into
+        ``merged`` (None: allocated here), one launch. Returns ``merged``."""
+        k, y = y if self.augment else (None, y)
+        tp = self.tta_plan(plan) if self.augment else None
+        A = int(y.shape[2]) if tp is None else tp.A_tot
+        if merged is None:
+            merged = torch.empty((len(plan.shapes), int(y.shape[1]), plan.S * A), dtype=torch.float32, device=y.device)
+        rows = plan.merge_rows(lo, lo + int(y.shape[0]))
+        if tp is None:
+            return _hip.tile_merge(y, rows, merged, A, self.cut_margin)
+        return _hip.tile_merge_tta(y, rows, merged, A, tp.branches[k], plan.canvas, self.cut_margin)
 
     def merge(self, y_chunks, plan):
         """merged [F, 4+nc, S*A] in frame pixels from the model calls' outputs (any grouping of ``plan.order`` into
-        consecutive calls): one ``_hip.tile_merge`` launch per call; every (frame, slot) is written exactly once."""
-        if not y_chunks or sum(int(y.shape[0]) for y in y_chunks) != len(plan):
-            raise ValueError(f"SlicedPredictor.merge: the chunks hold {sum(int(y.shape[0]) for y in y_chunks)} tiles, "
+        consecutive calls): one ``_hip.tile_merge`` launch per call; every (frame, slot) is written exactly once. With
+        ``augment`` a call is the tuple of its K branch outputs, A is the plan's A_tot and a call takes K
+        ``_hip.tile_merge_tta`` launches, each writing its branch's range of every slot the call names."""
+        y_chunks = list(y_chunks)
+        for c in y_chunks:
+            for y in (c if isinstance(c, (tuple, list)) else (c,)):
+                if not isinstance(y, torch.Tensor) or y.device.type != "cuda":
+                    raise RuntimeError("SlicedPredictor.merge: HIP kernel requires GPU tensors; no CPU fallback")
+        if self.augment:
+            K = len(self.tta_plan(plan))
+            if any(not isinstance(c, (tuple, list)) or len(c) != K for c in y_chunks):
+                raise ValueError(f"SlicedPredictor.merge: with augment a call is the tuple of its {K} branch outputs")
+            if any(len({int(y.shape[0]) for y in c}) != 1 for c in y_chunks):
+                raise ValueError("SlicedPredictor.merge: the branches of a call hold different numbers of tiles")
+        first = [c[0] if self.augment else c for c in y_chunks]
+        if not first or sum(int(y.shape[0]) for y in first) != len(plan):
+            raise ValueError(f"SlicedPredictor.merge: the chunks hold {sum(int(y.shape[0]) for y in first)} tiles, "
                              f"the plan {len(plan)}")
-        y0 = y_chunks[0]
-        if not isinstance(y0, torch.Tensor) or y0.device.type != "cuda":
-            raise RuntimeError("SlicedPredictor.merge: HIP kernel requires GPU tensors; no CPU fallback")
-        no, A = int(y0.shape[1]), int(y0.shape[2])
-        merged = torch.empty((len(plan.shapes), no, plan.S * A), dtype=torch.float32, device=y0.device)
-        lo = 0
-        for y in y_chunks:
-            hi = lo + int(y.shape[0])
-            _hip.tile_merge(y, plan.merge_rows(lo, hi), merged, A, self.cut_margin)
-            lo = hi
+        merged, lo = None, 0
+        for c, y0 in zip(y_chunks, first):
+            for y in (enumerate(c) if self.augment else (c,)):
+                merged = self._merge_into(merged, y, plan, lo)
+            lo += int(y0.shape[0])
         return merged
 
     def postprocess(self, merged, plan):
         """One NMS per frame over all its slots, boxes clipped to the frame: (out [F, max_det, 6], counts [F],
-        index [F, max_det] = slot * A + anchor)."""
+        index [F, max_det] = slot * A + anchor; with ``augment`` slot * A_tot + j, :meth:`locate`)."""
         out, counts, index = ops.non_max_suppression_padded(
             merged, self.conf, self.iou, classes=self.classes, agnostic=self.agnostic, multi_label=self.multi_label,
             max_det=self.max_det, max_wh=max(7680, max(max(s) for s in plan.shapes)), in_place=False)
@@ -293,7 +347,38 @@ class SlicedPredictor:
 
     @torch.inference_mode()
     def _predict(self, ts, plan):
-        return self.postprocess(self.merge(self.forward_tiles(ts, plan), plan), plan)
+        """The stages with every call (every branch of it) merged as soon as it has run: one output is alive at a time."""
+        merged = None
+        for lo, y in self._calls(ts, plan):
+            merged = self._merge_into(merged, y, plan, lo)
+        return self.postprocess(merged, plan)
+
+    def locate(self, index, plan):
+        """``(slot, branch, anchor)`` of a detection's ``index``: ``plan.slot(frame, slot)`` is its tile, ``anchor`` counts
+        along that branch's own output (branch 0 and the one output without ``augment``)."""
+        if self.augment:
+            tp = self.tta_plan(plan)
+            A = tp.A_tot
+        else:
+            A = self.model.tta_plan(plan.canvas, (1,), (None,)).branches[0].A  # the canvas' anchor count
+        index = int(index)
+        if not 0 <= index < plan.S * A:
+            raise IndexError(f"SlicedPredictor.locate: {index} outside [0, {plan.S} * {A})")
+        slot, j = divmod(index, A)
+        return (slot, *tp.locate(j)) if self.augment else (slot, 0, j)
+
+    def index(self, slot, branch, anchor, plan):
+        """Inverse of :meth:`locate`; None for an anchor that the augmentation's clip drops."""
+        if not 0 <= slot < plan.S:
+            raise IndexError(f"SlicedPredictor.index: slot {slot} outside [0, {plan.S})")
+        if self.augment:
+            tp = self.tta_plan(plan)
+            j = tp.index(branch, anchor)
+            return None if j is None else slot * tp.A_tot + j
+        A = self.model.tta_plan(plan.canvas, (1,), (None,)).branches[0].A
+        if branch != 0 or not 0 <= anchor < A:
+            raise IndexError(f"SlicedPredictor.index: branch {branch}, anchor {anchor} (one branch of {A} anchors)")
+        return slot * A + anchor
 
     def _start(self, frames):
         if not isinstance(frames, (list, tuple)):

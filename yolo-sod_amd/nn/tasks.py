@@ -595,13 +595,30 @@ class DetectionModel(BaseModel):
             raise RuntimeError(f"predict(augment=True): expected [B, C, H, W], got shape {tuple(x.shape)}")
         plan = self.tta_plan(x.shape[-2:], scales, flips)
         cat = None
-        for k, xi in enumerate(plan.make_views(x)):
-            yi = self._predict_once(xi)
-            yi = yi[0] if isinstance(yi, (list, tuple)) else yi
+        for k, yi in self.augment_branches(x, plan):
             if cat is None:
                 cat = torch.empty((yi.shape[0], yi.shape[1], plan.A_tot), dtype=torch.float32, device=yi.device)
             plan.merge(k, yi, cat)
         return cat, None
+
+    def augment_branches(self, x, plan):
+        """The branch loop of :meth:`_predict_augment` for a caller that places each branch itself (``SlicedPredictor``
+        puts it straight into frame pixels): yields ``(k, y_k)``, the Detect output [B, 4+nc, A_k] of branch k of
+        ``plan`` (``tta_plan(x.shape[-2:], ...)``) in that view's own pixels, nothing de-scaled or clipped yet. The
+        views are one ``_hip.tta_views`` launch; a branch's model call runs when the caller asks for it."""
+        if not isinstance(x, torch.Tensor) or x.device.type != "cuda":
+            raise RuntimeError("augment_branches: HIP kernel requires GPU tensors (got device "
+                               f"{getattr(x, 'device', type(x).__name__)}); no CPU fallback")
+        if x.dim() != 4 or tuple(int(v) for v in x.shape[-2:]) != plan.shape:
+            raise RuntimeError(f"augment_branches: x {tuple(x.shape)} is no [B, C, {plan.shape[0]}, {plan.shape[1]}] "
+                               "batch of the plan's shape")
+        for k, xi in enumerate(plan.make_views(x)):
+            yi = self._predict_once(xi)
+            yi = yi[0] if isinstance(yi, (list, tuple)) else yi
+            if int(yi.shape[-1]) != plan.branches[k].A:
+                raise RuntimeError(f"augment_branches: branch {k} has {int(yi.shape[-1])} anchors, "
+                                   f"{plan.branches[k].A} planned (strides {plan.strides})")
+            yield k, yi
 
     def _probe_strides(self, ch: int, s: int = 256) -> torch.Tensor:
         """Shape-only replica of the reference's 256x256 stride probe (tasks.py:369), on the meta device."""
