@@ -189,6 +189,29 @@ size_t yolosod_nms_workspace_v2(int B, int nc, int A, int multi_label, int max_d
 int yolosod_nms(float* pred, int B, int nc, int A, float conf_thres, double iou_thres, const int* classes,
                 int n_classes, int agnostic, int multi_label, int max_det, int max_nms, float max_wh, int in_place,
                 float* out, int* counts, int* out_index, void* workspace, size_t workspace_bytes, void* stream);
+/* Merge-NMS (the project's own definition, after the commented-out block ultralytics/utils/ops.py:299-309):
+ * yolosod_nms, then one more launch that replaces the box of every kept row k < counts[b] by the score-weighted mean
+ * of its cluster. Same arguments, workspace query and launches as yolosod_nms, plus n_merged: [B, max_det] int32.
+ *   - candidates: all of the image's candidates as NMS defines them (score > conf_thres, the class filter, best
+ *     class or with multi_label every class above conf_thres) - all n of them, not only the max_nms highest, and
+ *     without the reference comment's n < 3000 gate;
+ *   - membership: candidate j belongs to row k when NMS's own test says k would suppress it: torchvision's formula
+ *     in fp32 on the class-offset boxes (box + cls * max_wh, no offset with agnostic),
+ *     inter / ((area_k + area_j) - inter) > iou_thres (the comparison against the double threshold);
+ *   - row k's own candidate (its anchor and class) is always a member, also when its IoU with itself is NaN (a
+ *     zero-area box): the weight sum is never 0;
+ *   - merged coordinate c of x1, y1, x2, y2 (plain xyxy, no offset): sum_j (double)score_j * (double)c_j /
+ *     sum_j (double)score_j, accumulated and divided in fp64, rounded once to fp32; fixed summation order, no
+ *     atomics: two calls on the same input give the same bits;
+ *   - conf, cls, out_index, counts and the row order stay as NMS left them; rows >= counts[b] stay zero;
+ *   - n_merged[b][k]: the cluster's size, >= 1 for kept rows, 0 for padding (the reference's `redundant` filter
+ *     is n_merged > 1; it is not applied here).
+ * A cluster of one returns the kept box bit for bit ((s * c) / s is exact), so iou_thres = 1.0 is plain NMS.
+ * max_det 1..1024 (larger values are refused; yolosod_nms keeps its full range). */
+int yolosod_nms_merged(float* pred, int B, int nc, int A, float conf_thres, double iou_thres, const int* classes,
+                       int n_classes, int agnostic, int multi_label, int max_det, int max_nms, float max_wh,
+                       int in_place, float* out, int* counts, int* out_index, int* n_merged, void* workspace,
+                       size_t workspace_bytes, void* stream);
 
 /* BasePredictor.preprocess, non-tensor branch + LetterBox   ultralytics/engine/predictor.py:116-134, pre_transform
  * :145-161 (LetterBox: ultralytics/data/augment.py, restated in yolo-sod_amd/data/augment.py), one launch per batch.

@@ -48,6 +48,8 @@ SIGNATURES = {
     "yolosod_nms_workspace": (_sz, [_i, _i, _i, _i]),
     "yolosod_nms_workspace_v2": (_sz, [_i, _i, _i, _i, _i]),
     "yolosod_nms": (_i, [_vp, _i, _i, _i, _f, _d, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "yolosod_nms_merged": (_i, [_vp, _i, _i, _i, _f, _d, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _sz,
+                                _vp]),
     "yolosod_gemm_f32": (_i, [_vp, _l, _i, _vp, _l, _i, _i, _vp, _l, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "yolosod_layernorm": (_i, [_vp, _vp, _l, _i, _vp, _vp, _f, _vp]),
     "yolosod_attention": (_i, [_vp, _vp, _l, _i, _i, _i, _vp]),
@@ -665,6 +667,25 @@ def nms(pred, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, ma
     return _launch(("nms", (B, no - 4, A), int(multi_label)), pred.device, ops().nms_batched, pred, float(conf_thres),
                    float(iou_thres), cls, bool(agnostic), bool(multi_label), int(max_det), int(max_nms), float(max_wh),
                    bool(in_place))
+
+
+NMS_MERGE_MAX_DET = 1024  # yolosod_nms_merged: the merge launch holds an image's kept rows in one grid row of 8-row groups
+
+
+def nms_merged(pred, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, max_nms, max_wh, in_place,
+               n_merged=None):
+    """:func:`nms`, then every kept box replaced by the score-weighted mean of its cluster (merge-NMS, the definition
+    in include/yolosod_hip.h; torch.ops.yolosod.nms_merged_batched). Returns (out, counts, index, n_merged
+    [B, max_det] int32 = the clusters' sizes, 0 for padding rows). max_det 1..1024."""
+    B, no, A = _t(pred, "prediction").shape
+    if not 1 <= int(max_det) <= NMS_MERGE_MAX_DET:
+        raise ValueError(f"nms_merged: max_det={max_det} unsupported with merging (1..{NMS_MERGE_MAX_DET})")
+    cls = None
+    if classes is not None:
+        cls = torch.as_tensor(classes, dtype=torch.int32, device=pred.device).reshape(-1).contiguous()
+    return _launch(("nms", (B, no - 4, A), int(multi_label)), pred.device, ops().nms_merged_batched, pred,
+                   float(conf_thres), float(iou_thres), cls, bool(agnostic), bool(multi_label), int(max_det),
+                   int(max_nms), float(max_wh), bool(in_place), n_merged)
 
 
 def bias_act(y, bias, act, out=None, res=None, stats=None, out2=None, c2lo=0):

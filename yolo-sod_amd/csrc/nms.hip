@@ -23,6 +23,8 @@
 //               max_det boxes are kept and more candidates exist (keys >= T) does it sort that remainder and
 //               continue with the chunked in-LDS greedy (each chunk of 512 tested against the kept boxes, then
 //               its own IoU bitmask). Kept rows are written in parallel.
+//   nms_merge   (yolosod_nms_merged only) eight kept rows per workgroup against all of the image's candidates: each
+//               kept box becomes the score-weighted mean of the candidates it would suppress, summed in fp64.
 #include "common.h"
 #include <math.h>
 #include <stdlib.h>
@@ -1225,6 +1227,227 @@ __global__ __launch_bounds__(NMS_T) void nms_resolve_kernel(NmsArgs g) {
   YS_NSTAMP(10)
 }
 
+// -------------------------------------------------------------------------------------------------
+// nms_merge: every kept row's box becomes the score-weighted mean of its cluster (merge-NMS; after the reference's
+// commented-out block, ops.py:299-309). The project's own definition, include/yolosod_hip.h: the cluster of kept row k
+// is every candidate of the image (all n of nms_prep's, no max_nms cut, no cap) whose class-offset box has
+// IoU > iou_f with row k's (iou_gt's arithmetic), plus row k's own candidate whatever its IoU; each coordinate is
+// sum(score * c) / sum(score) over the plain xyxy boxes, accumulated and divided in fp64, rounded once to fp32.
+//
+// The candidates are read from amask / boxes / the scores, which nms_prep leaves intact; nms_resolve's remainder path
+// scatters its bucket order over keyA / posA, so the compaction no longer holds the whole set. amask is only
+// written for 256-anchor blocks with candidates (blkcnt != 0): the others are skipped, as nms_scatter does.
+//
+// grid = (ceil(max_det / MG_R), B). A workgroup holds MG_R kept rows in SGPRs and streams the image's anchors, one per
+// lane and block, four blocks with candidates per step (their loads in flight together, the next step's masks ahead),
+// with per-lane fp64 partial sums; then a butterfly over the wave's lanes and a sum over the four waves in wave order:
+// a fixed order, no atomics.
+// -------------------------------------------------------------------------------------------------
+constexpr int MG_R = 8;
+constexpr int MG_T = 256;
+constexpr int MG_U = 4;  // 256-anchor blocks in flight per step
+
+__global__ __launch_bounds__(MG_T) void nms_merge_kernel(NmsArgs g, int* __restrict__ n_merged) {
+  const int b = blockIdx.y;
+  const int row0 = (int)blockIdx.x * MG_R;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int cnt = __builtin_amdgcn_readfirstlane(g.counts[b]);
+  int* nm = n_merged + (long)b * g.max_det;
+  if (row0 >= cnt) {  // padding rows only (an image without detections: every workgroup)
+    if (tid < MG_R && row0 + tid < g.max_det) nm[row0 + tid] = 0;
+    return;
+  }
+  const long A = g.A;
+  const int nc = g.nc;
+  float* ob = g.out + ((long)b * g.max_det + row0) * 6;
+  const int* oi = g.out_index + (long)b * g.max_det + row0;
+  // the kept rows, wave-uniform: class-offset box and area as nms_select made them, anchor and class for the row's
+  // own candidate. Rows past counts[b] repeat row0 (their sums are dropped).
+  float kx1[MG_R], ky1[MG_R], kx2[MG_R], ky2[MG_R], kar[MG_R];
+  int kan[MG_R], kcl[MG_R];
+#pragma unroll
+  for (int r = 0; r < MG_R; ++r) {
+    const int rr = (row0 + r < cnt) ? r : 0;
+    const float* o = ob + rr * 6;
+    const float x1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(o[0])));
+    const float y1 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(o[1])));
+    const float x2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(o[2])));
+    const float y2 = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(o[3])));
+    const int cl = __builtin_amdgcn_readfirstlane((int)o[5]);
+    const float off = g.agnostic ? 0.0f : (float)cl * g.max_wh;
+    kx1[r] = x1 + off;
+    ky1[r] = y1 + off;
+    kx2[r] = x2 + off;
+    ky2[r] = y2 + off;
+    kar[r] = (kx2[r] - kx1[r]) * (ky2[r] - ky1[r]);
+    kan[r] = __builtin_amdgcn_readfirstlane(oi[rr]);
+    kcl[r] = cl;
+  }
+  const float thr_f = g.iou_f;
+  const bool all_pairs = !(g.iou >= 0.0);
+  const int nblk = (int)((A + 255) / 256);
+  const int* bc = g.blkcnt + (long)b * nblk;
+  const unsigned long long* am = g.amask + (long)b * A;
+  const float4* bx = g.boxes + (long)b * A;
+  const float* pb = g.pred + (long)b * (4 + nc) * A;
+
+  double sw[MG_R], sx1[MG_R], sy1[MG_R], sx2[MG_R], sy2[MG_R];
+  int cn[MG_R];
+#pragma unroll
+  for (int r = 0; r < MG_R; ++r) {
+    sw[r] = sx1[r] = sy1[r] = sx2[r] = sy2[r] = 0.0;
+    cn[r] = 0;
+  }
+
+  // the image's 256-anchor blocks with candidates, in order: 64 block counts per ballot
+  int nz_base = -64;
+  unsigned long long nz = 0ull;
+  auto next_block = [&]() -> int {  // wave-uniform; nblk when there is none left
+    while (nz == 0ull) {
+      nz_base += 64;
+      if (nz_base >= nblk) return nblk;
+      const int i = nz_base + lane;
+      nz = __ballot(i < nblk && bc[i] != 0);
+    }
+    const int q = __ffsll((long long)nz) - 1;
+    nz &= nz - 1ull;
+    return nz_base + q;
+  };
+  auto load_mask = [&](int blk) -> unsigned long long {
+    const long a = (long)blk * 256 + tid;
+    return (blk < nblk && a < A) ? am[a] : 0ull;
+  };
+  // MG_U blocks (4 x 256 anchors) per step: their masks were loaded during the previous step, their boxes and first
+  // scores are loaded together now, and the next step's masks go out before the arithmetic starts
+  int bl[MG_U];
+  unsigned long long mk[MG_U];
+#pragma unroll
+  for (int u = 0; u < MG_U; ++u) {
+    bl[u] = next_block();
+    mk[u] = load_mask(bl[u]);
+  }
+  while (bl[0] < nblk) {
+    float4 bb[MG_U];
+    float s0[MG_U];
+#pragma unroll
+    for (int u = 0; u < MG_U; ++u) {
+      bb[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+      s0[u] = 0.f;
+      if (mk[u]) {
+        const long a = (long)bl[u] * 256 + tid;
+        bb[u] = bx[a];
+        s0[u] = pb[(long)(4 + __ffsll((long long)mk[u]) - 1) * A + a];
+      }
+    }
+    int bn[MG_U];
+    unsigned long long mn[MG_U];
+#pragma unroll
+    for (int u = 0; u < MG_U; ++u) {
+      bn[u] = next_block();
+      mn[u] = load_mask(bn[u]);
+    }
+    // the lane's candidates of this step, block by block and in class order (one loop over all of them: a lane with a
+    // candidate in one block and a lane with one in another share an iteration)
+    unsigned fresh = (1u << MG_U) - 1u;  // bit u: block u's first class, whose score is s0[u], is still to come
+    while (true) {
+      int u = -1;
+#pragma unroll
+      for (int v = MG_U - 1; v >= 0; --v)
+        if (mk[v]) u = v;
+      if (u < 0) break;
+      unsigned long long m = 0ull;
+      float4 cbx = make_float4(0.f, 0.f, 0.f, 0.f);
+      float s = 0.f;
+      int blk = 0;
+#pragma unroll
+      for (int v = 0; v < MG_U; ++v)
+        if (u == v) {
+          m = mk[v];
+          cbx = bb[v];
+          s = s0[v];
+          blk = bl[v];
+        }
+      const int j = __ffsll((long long)m) - 1;
+      m &= m - 1ull;
+#pragma unroll
+      for (int v = 0; v < MG_U; ++v)
+        if (u == v) mk[v] = m;
+      const long a = (long)blk * 256 + tid;
+      if (!((fresh >> u) & 1u)) s = pb[(long)(4 + j) * A + a];
+      fresh &= ~(1u << u);
+      const float off = g.agnostic ? 0.0f : (float)j * g.max_wh;
+      const float4 cb = make_float4(cbx.x + off, cbx.y + off, cbx.z + off, cbx.w + off);
+      const float car = (cb.z - cb.x) * (cb.w - cb.y);
+      const double ds = (double)s;
+#pragma unroll
+      for (int r = 0; r < MG_R; ++r) {
+        const bool own = (int)a == kan[r] && j == kcl[r];
+        if (iou_gt_sparse(make_float4(kx1[r], ky1[r], kx2[r], ky2[r]), kar[r], cb, car, thr_f, all_pairs) || own) {
+          // a product of two floats is exact in fp64: each fma rounds once, as the product followed by an add would
+          sw[r] += ds;
+          sx1[r] = fma(ds, (double)cbx.x, sx1[r]);
+          sy1[r] = fma(ds, (double)cbx.y, sy1[r]);
+          sx2[r] = fma(ds, (double)cbx.z, sx2[r]);
+          sy2[r] = fma(ds, (double)cbx.w, sy2[r]);
+          ++cn[r];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < MG_U; ++u) {
+      bl[u] = bn[u];
+      mk[u] = mn[u];
+    }
+  }
+
+  // lanes (butterfly: every lane adds the same pairs in the same order), then the four waves in wave order
+  __shared__ double red[MG_T / 64][MG_R][5];
+  __shared__ int redn[MG_T / 64][MG_R];
+#pragma unroll
+  for (int r = 0; r < MG_R; ++r) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      sw[r] += __shfl_xor(sw[r], o, 64);
+      sx1[r] += __shfl_xor(sx1[r], o, 64);
+      sy1[r] += __shfl_xor(sy1[r], o, 64);
+      sx2[r] += __shfl_xor(sx2[r], o, 64);
+      sy2[r] += __shfl_xor(sy2[r], o, 64);
+      cn[r] += __shfl_xor(cn[r], o, 64);
+    }
+    if (lane == 0) {
+      red[wv][r][0] = sw[r];
+      red[wv][r][1] = sx1[r];
+      red[wv][r][2] = sy1[r];
+      red[wv][r][3] = sx2[r];
+      red[wv][r][4] = sy2[r];
+      redn[wv][r] = cn[r];
+    }
+  }
+  __syncthreads();
+  if (tid < MG_R && row0 + tid < g.max_det) {
+    const bool live = row0 + tid < cnt;
+    int n = 0;
+    if (live) {
+      double t[5];
+#pragma unroll
+      for (int c = 0; c < 5; ++c) {
+        t[c] = red[0][tid][c];
+#pragma unroll
+        for (int w = 1; w < MG_T / 64; ++w) t[c] += red[w][tid][c];
+      }
+#pragma unroll
+      for (int w = 0; w < MG_T / 64; ++w) n += redn[w][tid];
+      float* o = ob + tid * 6;
+      o[0] = (float)(t[1] / t[0]);
+      o[1] = (float)(t[2] / t[0]);
+      o[2] = (float)(t[3] / t[0]);
+      o[3] = (float)(t[4] / t[0]);
+    }
+    nm[row0 + tid] = n;
+  }
+}
+
 
 }  // namespace ys
 
@@ -1263,10 +1486,11 @@ YS_EXPORT size_t yolosod_nms_workspace(int B, int nc, int A, int multi_label) {
   return yolosod_nms_workspace_v2(B, nc, A, multi_label, NMS_MAXDET);
 }
 
-YS_EXPORT int yolosod_nms(float* pred, int B, int nc, int A, float conf_thres, double iou_thres, const int* classes,
-                          int n_classes, int agnostic, int multi_label, int max_det, int max_nms, float max_wh,
-                          int in_place, float* out, int* counts, int* out_index, void* workspace,
-                          size_t workspace_bytes, void* stream) {
+// the five NMS launches, then (n_merged != nullptr) the merge launch, on one workspace carve
+static int nms_run(float* pred, int B, int nc, int A, float conf_thres, double iou_thres, const int* classes,
+                   int n_classes, int agnostic, int multi_label, int max_det, int max_nms, float max_wh, int in_place,
+                   float* out, int* counts, int* out_index, int* n_merged, void* workspace, size_t workspace_bytes,
+                   void* stream) {
   YS_CHECK_ARG(pred && out && counts && out_index, "nms: null pointer");
   YS_CHECK_ARG(nc >= 1 && nc <= 64, "nms: nc=%d unsupported (1..64)", nc);
   YS_CHECK_ARG(max_det >= 1 && max_det <= NMS_MAXDET_BIG, "nms: max_det=%d unsupported (1..%d)", max_det,
@@ -1331,6 +1555,27 @@ YS_EXPORT int yolosod_nms(float* pred, int B, int nc, int A, float conf_thres, d
     hipLaunchKernelGGL(nms_resolve_kernel<true>, dim3(B), dim3(NMS_T), 0, st, g);
   else
     hipLaunchKernelGGL(nms_resolve_kernel<false>, dim3(B), dim3(NMS_T), 0, st, g);
+  if (n_merged)
+    hipLaunchKernelGGL(nms_merge_kernel, dim3((max_det + MG_R - 1) / MG_R, B), dim3(MG_T), 0, st, g, n_merged);
   YS_CHECK_LAUNCH("nms");
   return 0;
+}
+
+YS_EXPORT int yolosod_nms(float* pred, int B, int nc, int A, float conf_thres, double iou_thres, const int* classes,
+                          int n_classes, int agnostic, int multi_label, int max_det, int max_nms, float max_wh,
+                          int in_place, float* out, int* counts, int* out_index, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  return nms_run(pred, B, nc, A, conf_thres, iou_thres, classes, n_classes, agnostic, multi_label, max_det, max_nms,
+                 max_wh, in_place, out, counts, out_index, nullptr, workspace, workspace_bytes, stream);
+}
+
+YS_EXPORT int yolosod_nms_merged(float* pred, int B, int nc, int A, float conf_thres, double iou_thres,
+                                 const int* classes, int n_classes, int agnostic, int multi_label, int max_det,
+                                 int max_nms, float max_wh, int in_place, float* out, int* counts, int* out_index,
+                                 int* n_merged, void* workspace, size_t workspace_bytes, void* stream) {
+  YS_CHECK_ARG(n_merged, "nms_merged: null pointer");
+  YS_CHECK_ARG(max_det >= 1 && max_det <= NMS_MAXDET, "nms_merged: max_det=%d unsupported with merging (1..%d)",
+               max_det, NMS_MAXDET);
+  return nms_run(pred, B, nc, A, conf_thres, iou_thres, classes, n_classes, agnostic, multi_label, max_det, max_nms,
+                 max_wh, in_place, out, counts, out_index, n_merged, workspace, workspace_bytes, stream);
 }

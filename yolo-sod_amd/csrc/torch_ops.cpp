@@ -1,6 +1,6 @@
 // Torch-op registration of the hot-path kernel families ("a torch.utils.cpp_extension module ... thin
 // wrappers registered as torch ops"): torch.ops.yolosod.{se_fwd, cbam_fwd, ca_fwd, a2_fwd, swin_fwd,
-// detect_head_fwd, detect_decode_fwd, nms_batched, stem_fwd, tta_views, tta_merge}.
+// detect_head_fwd, detect_decode_fwd, nms_batched, nms_merged_batched, stem_fwd, tta_views, tta_merge}.
 //
 // Each op validates its tensors with TORCH_CHECK (RuntimeError in Python, as the reference's own asserts /
 // exceptions surface, e.g. a2_attn.py:24), allocates its output and workspace with at::empty on the input's device
@@ -425,6 +425,54 @@ std::tuple<Tensor, Tensor, Tensor> nms_batched(const Tensor& pred, double conf_t
   return {out, counts, index};
 }
 
+// Merge-NMS (yolosod_nms_merged): nms_batched plus n_merged [B, max_det] int32, the size of every kept row's cluster;
+// the rows' boxes are the clusters' score-weighted means. n_merged may be passed in (it is then the fourth result).
+std::tuple<Tensor, Tensor, Tensor, Tensor> nms_merged_batched(const Tensor& pred, double conf_thres, double iou_thres,
+                                                              const c10::optional<Tensor>& classes, bool agnostic,
+                                                              bool multi_label, int64_t max_det, int64_t max_nms,
+                                                              double max_wh, bool in_place,
+                                                              const c10::optional<Tensor>& n_merged) {
+  TORCH_CHECK(pred.is_cuda(), "nms_merged_batched: HIP kernel requires a GPU tensor (got ", pred.device(),
+              "); no CPU fallback");
+  TORCH_CHECK(pred.scalar_type() == at::kFloat && pred.is_contiguous() && pred.dim() == 3,
+              "nms_merged_batched: prediction must be a contiguous float32 GPU tensor [B, 4+nc, A], got ", pred.sizes());
+  TORCH_CHECK(max_det >= 1 && max_det <= 1024, "nms_merged_batched: max_det=", max_det,
+              " unsupported with merging (1..1024)");
+  c10::DeviceGuard guard(pred.device());
+  const int B = pred.size(0), nc = pred.size(1) - 4, A = pred.size(2);
+  auto f = pred.options();
+  Tensor nm;
+  if (n_merged) {
+    TORCH_CHECK(n_merged->device() == pred.device() && n_merged->scalar_type() == at::kInt &&
+                    n_merged->is_contiguous() && n_merged->dim() == 2 && n_merged->size(0) == B &&
+                    n_merged->size(1) == max_det,
+                "nms_merged_batched: n_merged must be a contiguous int32 [", B, ", ", max_det,
+                "] tensor on the prediction's device, got ", n_merged->sizes(), " on ", n_merged->device());
+    nm = *n_merged;
+  } else {
+    nm = at::empty({B, max_det}, f.dtype(at::kInt));
+  }
+  Tensor out = at::empty({B, max_det, 6}, f);
+  Tensor counts = at::empty({B}, f.dtype(at::kInt));
+  Tensor index = at::empty({B, max_det}, f.dtype(at::kInt));
+  Tensor ws = workspace(yolosod_nms_workspace_v2(B, nc, A, multi_label, max_det), pred);
+  const int* cls = nullptr;
+  int ncls = 0;
+  if (classes) {
+    TORCH_CHECK(classes->device() == pred.device() && classes->scalar_type() == at::kInt && classes->is_contiguous(),
+                "nms_merged_batched: classes must be a contiguous int32 tensor on the prediction's device");
+    cls = classes->data_ptr<int>();
+    ncls = classes->numel();
+  }
+  auto st = c10::hip::getCurrentHIPStream(pred.get_device());
+  check_rc(yolosod_nms_merged(pred.data_ptr<float>(), B, nc, A, (float)conf_thres, iou_thres, cls, ncls, agnostic,
+                              multi_label, max_det, max_nms, (float)max_wh, in_place ? 1 : 0, out.data_ptr<float>(),
+                              counts.data_ptr<int>(), index.data_ptr<int>(), nm.data_ptr<int>(), ws.data_ptr(),
+                              ws.numel(), sp(st)),
+           "nms_merged_batched");
+  return {out, counts, index, nm};
+}
+
 // The stem (layer 0): (SiLU(conv3x3 / stride 2 / pad 1 (x, weight) + bias), the output's plane partial sums for the SE
 // after it). fp32 only; the shapes are the caller's to check (_hip.stem_ok), the C ABI checks them again.
 std::tuple<Tensor, Tensor> stem_fwd(const Tensor& x, const Tensor& weight, const Tensor& bias) {
@@ -527,6 +575,9 @@ TORCH_LIBRARY(yolosod, m) {
   m.def("detect_decode_fwd(Tensor[] maps, float[] strides, int nc, int reg_max) -> Tensor");
   m.def("nms_batched(Tensor(a!) pred, float conf_thres, float iou_thres, Tensor? classes, bool agnostic, "
         "bool multi_label, int max_det, int max_nms, float max_wh, bool in_place=True) -> (Tensor, Tensor, Tensor)");
+  m.def("nms_merged_batched(Tensor(a!) pred, float conf_thres, float iou_thres, Tensor? classes, bool agnostic, "
+        "bool multi_label, int max_det, int max_nms, float max_wh, bool in_place=True, Tensor(b!)? n_merged=None) "
+        "-> (Tensor, Tensor, Tensor, Tensor)");
   m.def("stem_fwd(Tensor x, Tensor weight, Tensor bias) -> (Tensor, Tensor)");
   m.def("tta_views(Tensor x, Tensor desc, Tensor(a!)[] outs, int[] geom) -> ()");
   m.def("tta_merge(Tensor y, Tensor(a!) cat, int src_lo, int n, int dst, float scale, int flip, int img_h, "
@@ -546,9 +597,19 @@ TORCH_LIBRARY_IMPL(yolosod, CUDA, m) {
   m.impl("detect_head_into", detect_head_into);
   m.impl("detect_decode_fwd", detect_decode_fwd);
   m.impl("nms_batched", nms_batched);
+  m.impl("nms_merged_batched", nms_merged_batched);
   m.impl("stem_fwd", stem_fwd);
   m.impl("tta_views", tta_views);
   m.impl("tta_merge", tta_merge);
+}
+
+TORCH_LIBRARY_IMPL(yolosod, CPU, m) {
+  m.impl("nms_merged_batched", [](const Tensor& pred, double, double, const c10::optional<Tensor>&, bool, bool, int64_t,
+                                  int64_t, double, bool, const c10::optional<Tensor>&)
+                                   -> std::tuple<Tensor, Tensor, Tensor, Tensor> {
+    TORCH_CHECK(false, "nms_merged_batched: HIP kernel requires a GPU tensor (got ", pred.device(),
+                "); no CPU fallback");
+  });
 }
 
 TORCH_LIBRARY_IMPL(yolosod, Meta, m) {
@@ -585,6 +646,13 @@ TORCH_LIBRARY_IMPL(yolosod, Meta, m) {
     auto f = pred.options();
     return std::make_tuple(at::empty({B, max_det, 6}, f), at::empty({B}, f.dtype(at::kInt)),
                            at::empty({B, max_det}, f.dtype(at::kInt)));
+  });
+  m.impl("nms_merged_batched", [](const Tensor& pred, double, double, const c10::optional<Tensor>&, bool, bool,
+                                  int64_t max_det, int64_t, double, bool, const c10::optional<Tensor>&) {
+    const int64_t B = pred.size(0);
+    auto f = pred.options();
+    return std::make_tuple(at::empty({B, max_det, 6}, f), at::empty({B}, f.dtype(at::kInt)),
+                           at::empty({B, max_det}, f.dtype(at::kInt)), at::empty({B, max_det}, f.dtype(at::kInt)));
   });
   m.impl("stem_fwd", [](const Tensor& x, const Tensor& weight, const Tensor&) {
     const int64_t B = x.size(0), C = weight.size(0), H = x.size(2) / 2, W = x.size(3) / 2;

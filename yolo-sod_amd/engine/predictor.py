@@ -83,9 +83,14 @@ def frames_to_device(frames, device, who="DetectionPredictor"):
 
 class DetectionPredictor:
     def __init__(self, model, conf=0.25, iou=0.7, max_det=300, classes=None, agnostic_nms=False,
-                 multi_label=False, imgsz=640, rect=None, augment=False):
+                 multi_label=False, imgsz=640, rect=None, augment=False, merge_nms=False):
         self.model = model
         self.conf, self.iou, self.max_det = conf, iou, max_det
+        # merge-NMS (ops.non_max_suppression_padded(merge=True)): kept boxes are their clusters' score-weighted means,
+        # merged in canvas pixels before the boxes are mapped and clipped; ``n_merged`` [B, max_det] int32 of the last
+        # batch (the clusters' sizes, a device tensor) stays on the predictor, None until then and without merge_nms
+        self.merge_nms = bool(merge_nms)
+        self.n_merged = None
         self.classes, self.agnostic, self.multi_label = classes, agnostic_nms, multi_label
         # test-time augmentation (DetectionModel._predict_augment: three views, one concatenated prediction tensor in
         # canvas pixels, so NMS and everything after it are the same; ``index`` then counts along that concatenation:
@@ -137,14 +142,22 @@ class DetectionPredictor:
         preds = self.model(x, augment=True) if self.augment else self.model(x)
         return preds[0] if isinstance(preds, (list, tuple)) else preds
 
+    def _nms(self, y):
+        """NMS of the prediction tensor y as this predictor is set up (in_place=False); with ``merge_nms`` the merged
+        rows, ``n_merged`` kept on the predictor."""
+        res = ops.non_max_suppression_padded(
+            y, self.conf, self.iou, classes=self.classes, agnostic=self.agnostic, multi_label=self.multi_label,
+            max_det=self.max_det, in_place=False, merge=self.merge_nms)
+        if self.merge_nms:
+            self.n_merged = res[3]
+        return res[:3]
+
     def _predict_ingested(self, ing: Ingested):
         """The model, NMS and the boxes back in each frame's pixels (predict.py:23-41: scale_boxes(img.shape[2:], boxes,
         orig_img.shape) per image) as one more launch on the padded rows."""
         preds = self._forward(ing.x)
         y = preds[0] if isinstance(preds, (list, tuple)) else preds
-        out, counts, index = ops.non_max_suppression_padded(
-            y, self.conf, self.iou, classes=self.classes, agnostic=self.agnostic, multi_label=self.multi_label,
-            max_det=self.max_det, in_place=False)
+        out, counts, index = self._nms(y)
         _hip.scale_boxes_padded(out, counts, ing.geom)
         return out, counts, index
 
@@ -158,9 +171,7 @@ class DetectionPredictor:
         y = self._forward(x)
         # in_place=False: the reference's postprocess rewrites preds[:, :4] to xyxy (ops.py:167, in_place=True) and
         # then drops preds; y is local here too, so the rewrite (17 MB at bs 32) is skipped - same detections
-        out, counts, index = ops.non_max_suppression_padded(
-            y, self.conf, self.iou, classes=self.classes, agnostic=self.agnostic, multi_label=self.multi_label,
-            max_det=self.max_det, in_place=False)
+        out, counts, index = self._nms(y)
         ops.clip_boxes(out[..., :4], x.shape[2:])  # scale_boxes with gain 1 / pad 0 (same-shape tensor input)
         return out, counts, index
 
@@ -220,12 +231,19 @@ class SlicedPredictor:
 
     ``cut_margin`` (tile pixels; None: off): a candidate whose box comes within it of a tile edge that is interior to
     the frame is dropped before NMS - the tile saw the object truncated, a neighbouring tile or the whole-frame slot
-    sees it whole. ``merged`` takes F * (4+nc) * S * A * 4 bytes."""
+    sees it whole. ``merged`` takes F * (4+nc) * S * A * 4 bytes.
+
+    ``merge_nms=True``: the one NMS is a merge-NMS (``ops.non_max_suppression_padded(merge=True)``): an object seen by
+    several tiles, the whole frame and the augmented views gives one row whose box is the score-weighted mean of all of
+    them, in frame pixels; the clusters' sizes of the last batch are ``n_merged`` [F, max_det] int32."""
 
     def __init__(self, model, slice=640, overlap=0.2, full_frame=True, cut_margin=None, batch=32, conf=0.25, iou=0.7,
                  max_det=300, classes=None, agnostic_nms=False, multi_label=False, imgsz=640, augment=False, scales=None,
-                 flips=None):
+                 flips=None, merge_nms=False):
         self.model = model
+        # merge-NMS in frame pixels, before the clip to the frame; ``n_merged`` [F, max_det] int32 of the last batch
+        self.merge_nms = bool(merge_nms)
+        self.n_merged = None
         self.augment = bool(augment)
         if not self.augment and (scales is not None or flips is not None):
             raise ValueError("SlicedPredictor: scales / flips are the views of augment=True")
@@ -338,9 +356,13 @@ class SlicedPredictor:
     def postprocess(self, merged, plan):
         """One NMS per frame over all its slots, boxes clipped to the frame: (out [F, max_det, 6], counts [F],
         index [F, max_det] = slot * A + anchor; with ``augment`` slot * A_tot + j, :meth:`locate`)."""
-        out, counts, index = ops.non_max_suppression_padded(
+        res = ops.non_max_suppression_padded(
             merged, self.conf, self.iou, classes=self.classes, agnostic=self.agnostic, multi_label=self.multi_label,
-            max_det=self.max_det, max_wh=max(7680, max(max(s) for s in plan.shapes)), in_place=False)
+            max_det=self.max_det, max_wh=max(7680, max(max(s) for s in plan.shapes)), in_place=False,
+            merge=self.merge_nms)
+        out, counts, index = res[:3]
+        if self.merge_nms:
+            self.n_merged = res[3]
         geom = torch.tensor([[1.0, 0.0, 0.0, w, h] for h, w in plan.shapes], dtype=torch.float32)
         _hip.scale_boxes_padded(out, counts, geom.pin_memory().to(out.device, non_blocking=True))
         return out, counts, index

@@ -89,23 +89,35 @@ def _validate(prediction, conf_thres, iou_thres, labels, rotated, nc):
 
 def non_max_suppression_padded(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False,
                                multi_label=False, labels=(), max_det=300, nc=0, max_time_img=0.05, max_nms=30000,
-                               max_wh=7680, in_place=True, rotated=False):
+                               max_wh=7680, in_place=True, rotated=False, merge=False):
     """Same semantics as :func:`non_max_suppression`, returning fixed-shape device tensors and never syncing:
-    ``(out [B, max_det, 6], counts [B] int32, index [B, max_det] int32 anchor ids, -1 padded)``."""
+    ``(out [B, max_det, 6], counts [B] int32, index [B, max_det] int32 anchor ids, -1 padded)``.
+
+    ``merge=True`` (merge-NMS, after the reference's commented-out block ``ops.py:299-309``): the box of every kept row
+    becomes the score-weighted mean of its cluster - all of the image's candidates that the row would suppress (IoU >
+    ``iou_thres`` on the class-offset boxes) and the row's own candidate - summed in fp64; ``conf``, ``cls``,
+    ``index``, ``counts`` and the order stay. Returns ``(out, counts, index, n_merged [B, max_det] int32)``, the
+    clusters' sizes (0 for padding rows; the reference's ``redundant`` filter is ``n_merged > 1``). Unlike the
+    reference's comment it uses every candidate (no ``max_nms`` cut, no ``n < 3000`` gate) and a kept row's own
+    candidate always counts. ``max_det`` up to 1024."""
     prediction, nc = _validate(prediction, conf_thres, iou_thres, labels, rotated, nc)
     if prediction.shape[-1] == 6:
         raise NotImplementedError("end-to-end (B, N, 6) predictions are not on this path")
     multi_label = bool(multi_label) and nc > 1
+    if merge:
+        return _hip.nms_merged(prediction, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, max_nms,
+                               max_wh, in_place)
     return _hip.nms(prediction, conf_thres, iou_thres, classes, agnostic, multi_label, max_det, max_nms, max_wh,
                     in_place)
 
 
 def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False,
                         multi_label=False, labels=(), max_det=300, nc=0, max_time_img=0.05, max_nms=30000,
-                        max_wh=7680, in_place=True, rotated=False):
-    """Reference-compatible NMS (ops.py:167-316): list of [n_i, 6] tensors (x1, y1, x2, y2, conf, cls)."""
-    out, counts, _ = non_max_suppression_padded(prediction, conf_thres, iou_thres, classes, agnostic, multi_label,
-                                                labels, max_det, nc, max_time_img, max_nms, max_wh, in_place,
-                                                rotated)
+                        max_wh=7680, in_place=True, rotated=False, merge=False):
+    """Reference-compatible NMS (ops.py:167-316): list of [n_i, 6] tensors (x1, y1, x2, y2, conf, cls); with
+    ``merge=True`` the rows' boxes are their clusters' score-weighted means (:func:`non_max_suppression_padded`)."""
+    out, counts = non_max_suppression_padded(prediction, conf_thres, iou_thres, classes, agnostic, multi_label,
+                                             labels, max_det, nc, max_time_img, max_nms, max_wh, in_place,
+                                             rotated, merge)[:2]
     n = counts.cpu().tolist()  # the one host sync (the reference's output sizes are data dependent too)
     return [out[i, : n[i]] for i in range(len(n))]
