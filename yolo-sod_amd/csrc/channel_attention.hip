@@ -17,6 +17,11 @@
 // launch boundaries and the smaller grids cost more - SE L1 0.269 vs 0.243 ms, CBAM L4 0.199 vs 0.163, CA L32 0.090
 // vs 0.073 - so every pass covers the whole batch.)
 //
+// NaN: every max, the MLP's ReLU and CA's h_sigmoid clamp are the IEEE 754-2019 maximum / minimum (common.h nmax_ /
+// nmin_), so a NaN activation reaches the gates it reaches in the reference (relu, AdaptiveMaxPool2d, torch.max and
+// ReLU6 all hand it on): the whole image for SE and CBAM, the NaN's row and column in every channel for CA. fmaxf /
+// fminf returned the other operand and gave a finite gate. NaN-free inputs give the same bits as before.
+//
 // Reference semantics (file:line in quitedob/yolo-sod):
 //   SE     ultralytics/nn/modules/smallobj_modules.py:84-92  (x * sigmoid(fc2(relu(fc1(mean_hw x)))))
 //   CBAM   ultralytics/nn/modules/cbam_block.py:19-55         ((x*ca)*sa, ca from avg+max MLP, sa = 7x7 conv)
@@ -70,25 +75,25 @@ __global__ __launch_bounds__(256) void plane_part_stats_kernel(const T* __restri
       s += ((a.x + a.y) + (a.z + a.w)) + ((b.x + b.y) + (b.z + b.w)) + ((c.x + c.y) + (c.z + c.w)) +
            ((d.x + d.y) + (d.z + d.w));
       if (WITH_MAX) {
-        m = fmaxf(m, fmaxf(fmaxf(fmaxf(a.x, a.y), fmaxf(a.z, a.w)), fmaxf(fmaxf(b.x, b.y), fmaxf(b.z, b.w))));
-        m = fmaxf(m, fmaxf(fmaxf(fmaxf(c.x, c.y), fmaxf(c.z, c.w)), fmaxf(fmaxf(d.x, d.y), fmaxf(d.z, d.w))));
+        m = nmax_(m, nmax_(nmax4_(a.x, a.y, a.z, a.w), nmax4_(b.x, b.y, b.z, b.w)));
+        m = nmax_(m, nmax_(nmax4_(c.x, c.y, c.z, c.w), nmax4_(d.x, d.y, d.z, d.w)));
       }
     }
     for (; i < n4; i += 256) {
       f32x4 a = ld4(p4 + 4 * i);
       s += (a.x + a.y) + (a.z + a.w);
-      if (WITH_MAX) m = fmaxf(m, fmaxf(fmaxf(a.x, a.y), fmaxf(a.z, a.w)));
+      if (WITH_MAX) m = nmax_(m, nmax4_(a.x, a.y, a.z, a.w));
     }
   } else {
     for (long i = s0 + tid; i < s1; i += 256) {
       float v = ld1(p + i);
       s += v;
-      if (WITH_MAX) m = fmaxf(m, v);
+      if (WITH_MAX) m = nmax_(m, v);
     }
   }
   __shared__ float ss[4], sm[4];
   s = wave_sum(s);
-  if (WITH_MAX) m = wave_max(m);
+  if (WITH_MAX) m = wave_nmax(m);
   const int w = tid >> 6;
   if ((tid & 63) == 0) {
     ss[w] = s;
@@ -97,7 +102,7 @@ __global__ __launch_bounds__(256) void plane_part_stats_kernel(const T* __restri
   __syncthreads();
   if (tid == 0) {
     psum[blockIdx.x] = (ss[0] + ss[1]) + (ss[2] + ss[3]);
-    if (WITH_MAX) pmax[blockIdx.x] = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+    if (WITH_MAX) pmax[blockIdx.x] = nmax4_(sm[0], sm[1], sm[2], sm[3]);
   }
 }
 
@@ -133,12 +138,12 @@ __device__ __forceinline__ void gate_mlp(const float* __restrict__ psum, const f
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         s += v[u];
-        if (CBAM) m = fmaxf(m, w[u]);
+        if (CBAM) m = nmax_(m, w[u]);
       }
     }
     for (; k < parts; ++k) {
       s += ps[k];
-      if (CBAM) m = fmaxf(m, pm[k]);
+      if (CBAM) m = nmax_(m, pm[k]);
     }
     avg[c] = s * inv_hw;
     if (CBAM) mx[c] = m;
@@ -151,7 +156,7 @@ __device__ __forceinline__ void gate_mlp(const float* __restrict__ psum, const f
     float acc = 0.f;
     for (int k = lane; k < C; k += 64) acc += w1[(long)jj * C + k] * v[k];
     acc = wave_sum(acc);
-    if (lane == 0) hsh[(j < hid ? 0 : 64) + jj] = fmaxf(CBAM ? acc : acc + b1[jj], 0.f);
+    if (lane == 0) hsh[(j < hid ? 0 : 64) + jj] = nmax_(CBAM ? acc : acc + b1[jj], 0.f);
   }
   __syncthreads();
   for (int i = tid; i < n; i += 256) {
@@ -305,7 +310,7 @@ __global__ __launch_bounds__(256) void cbam_pixel_stats_kernel(const T* __restri
       for (int u = 0; u < 8; ++u) {
         const f32x4 o = cab[c + u] * v0[u];
         s += o;
-        m.x = fmaxf(m.x, o.x); m.y = fmaxf(m.y, o.y); m.z = fmaxf(m.z, o.z); m.w = fmaxf(m.w, o.w);
+        m.x = nmax_(m.x, o.x); m.y = nmax_(m.y, o.y); m.z = nmax_(m.z, o.z); m.w = nmax_(m.w, o.w);
       }
       c += 8;
     }
@@ -317,13 +322,13 @@ __global__ __launch_bounds__(256) void cbam_pixel_stats_kernel(const T* __restri
       for (int u = 0; u < 8; ++u) {
         const f32x4 o = cab[c + u] * v[u];
         s += o;
-        m.x = fmaxf(m.x, o.x); m.y = fmaxf(m.y, o.y); m.z = fmaxf(m.z, o.z); m.w = fmaxf(m.w, o.w);
+        m.x = nmax_(m.x, o.x); m.y = nmax_(m.y, o.y); m.z = nmax_(m.z, o.z); m.w = nmax_(m.w, o.w);
       }
     }
     for (; c < c1; ++c) {
       const f32x4 o = cab[c] * ld4(xb + (long)c * HW);
       s += o;
-      m.x = fmaxf(m.x, o.x); m.y = fmaxf(m.y, o.y); m.z = fmaxf(m.z, o.z); m.w = fmaxf(m.w, o.w);
+      m.x = nmax_(m.x, o.x); m.y = nmax_(m.y, o.y); m.z = nmax_(m.z, o.z); m.w = nmax_(m.w, o.w);
     }
     *reinterpret_cast<f32x4*>(sp) = s;
     *reinterpret_cast<f32x4*>(sp + HW) = m;
@@ -338,13 +343,13 @@ __global__ __launch_bounds__(256) void cbam_pixel_stats_kernel(const T* __restri
       for (int u = 0; u < 8; ++u) {
         const float o = cab[c + u] * v[u];
         s += o;
-        m = fmaxf(m, o);
+        m = nmax_(m, o);
       }
     }
     for (; c < c1; ++c) {
       const float o = cab[c] * ld1(xb + (long)c * HW);
       s += o;
-      m = fmaxf(m, o);
+      m = nmax_(m, o);
     }
     sp[0] = s;
     sp[HW] = m;
@@ -370,12 +375,12 @@ __device__ __forceinline__ float2 cbam_map_at(const float* __restrict__ mp, int 
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         s += a[u];
-        m = fmaxf(m, c[u]);
+        m = nmax_(m, c[u]);
       }
     }
     for (; g < G; ++g) {
       s += q[(long)(2 * g) * HW];
-      m = fmaxf(m, q[(long)(2 * g + 1) * HW]);
+      m = nmax_(m, q[(long)(2 * g + 1) * HW]);
     }
     s *= invC;
   }
@@ -434,7 +439,7 @@ __global__ __launch_bounds__(256) void cbam_sa_kernel(const float* __restrict__ 
       for (int u = 0; u < 4; ++u)
         if (g0 + u < G) {
           sm[k] += a[k][u];
-          mx[k] = fmaxf(mx[k], c[k][u]);
+          mx[k] = nmax_(mx[k], c[k][u]);
         }
   }
 #pragma unroll
@@ -620,7 +625,7 @@ __global__ __launch_bounds__(256) void ca_gate_kernel(const float* __restrict__ 
     float z = acc + b1[j];
     const float inv = 1.0f / sqrtf(bn_v[j] + bn_eps);
     z = (z - bn_m[j]) * inv * bn_w[j] + bn_b[j];
-    z = fminf(fmaxf(z + 3.0f, 0.0f), 6.0f) / 6.0f;
+    z = nmin_(nmax_(z + 3.0f, 0.0f), 6.0f) / 6.0f;
     ts[pp * (mip + 1) + j] = z;
   }
   __syncthreads();

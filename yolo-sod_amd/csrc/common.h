@@ -267,6 +267,15 @@ __device__ __forceinline__ void split8(f32x4 a, f32x4 b, f16x8_t& h, f16x8_t& l)
 // (maxNum) would return the non-NaN operand and lose it, so a NaN produced upstream (e.g. a Swin block fed to the Detect
 // head) would go unflagged. Same instruction count as the fmaxf form.
 __device__ __forceinline__ float nmax_(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+// The same forms for the channel-attention maxes and clamps (channel_attention.hip, the producers' pmax): the
+// reference's relu / AdaptiveMaxPool2d / torch.max / ReLU6 all hand a NaN on, fmaxf / fminf would return the other operand.
+__device__ __forceinline__ float nmin_(float a, float b) { return __builtin_elementwise_minimum(a, b); }
+__device__ __forceinline__ float nmax4_(float a, float b, float c, float d) { return nmax_(nmax_(a, b), nmax_(c, d)); }
+__device__ __forceinline__ float wave_nmax(float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = nmax_(v, __shfl_xor(v, o, 64));
+  return v;
+}
 __device__ __forceinline__ float range_acc(float m, f32x4 v) {
   return nmax_(nmax_(m, nmax_(fabsf(v.x), fabsf(v.y))), nmax_(fabsf(v.z), fabsf(v.w)));
 }

@@ -180,7 +180,7 @@ __global__ __launch_bounds__(NT, 2) void conv1x1_x2_kernel(Args p) {
               v, reinterpret_cast<f32x4*>(p.y2 + (long)b * p.y2bs + (long)(o - p.c2lo) * HW + px));
         if (STATS) {  // pixels past HW were staged as copies of the last pixel: not counted
           ts += (v[0] + v[1]) + (v[2] + v[3]);
-          if (STATS == 2) tm = fmaxf(tm, fmaxf(fmaxf(v[0], v[1]), fmaxf(v[2], v[3])));
+          if (STATS == 2) tm = nmax_(tm, nmax4_(v[0], v[1], v[2], v[3]));  // NaN-propagating (common.h nmax_)
         }
       }
     }
@@ -188,8 +188,8 @@ __global__ __launch_bounds__(NT, 2) void conv1x1_x2_kernel(Args p) {
       ts += __shfl_xor(ts, 16, 64);
       ts += __shfl_xor(ts, 32, 64);
       if (STATS == 2) {
-        tm = fmaxf(tm, __shfl_xor(tm, 16, 64));
-        tm = fmaxf(tm, __shfl_xor(tm, 32, 64));
+        tm = nmax_(tm, __shfl_xor(tm, 16, 64));
+        tm = nmax_(tm, __shfl_xor(tm, 32, 64));
       }
       if (g == 0) {
         const long ti = ((long)b * p.cout + o) * p.ntile + tile;

@@ -126,7 +126,7 @@ __global__ __launch_bounds__(256) void bias_act_stats_kernel(const T* __restrict
         unpack8(ob, f);  // statistics of the stored (rounded) values
         s += ((f[0] + f[1]) + (f[2] + f[3])) + ((f[4] + f[5]) + (f[6] + f[7]));
         if (MAX)
-          m = fmaxf(m, fmaxf(fmaxf(fmaxf(f[0], f[1]), fmaxf(f[2], f[3])), fmaxf(fmaxf(f[4], f[5]), fmaxf(f[6], f[7]))));
+          m = nmax_(m, nmax_(nmax4_(f[0], f[1], f[2], f[3]), nmax4_(f[4], f[5], f[6], f[7])));
       }
     }
   } else
@@ -153,12 +153,12 @@ __global__ __launch_bounds__(256) void bias_act_stats_kernel(const T* __restrict
       // statistics of the stored values (bf16 storage: of the rounded values, as a consumer re-reading out sees)
       if (sizeof(T) == 2) o = round_bf16(o);
       s += (o.x + o.y) + (o.z + o.w);
-      if (MAX) m = fmaxf(m, fmaxf(fmaxf(o.x, o.y), fmaxf(o.z, o.w)));
+      if (MAX) m = nmax_(m, nmax4_(o.x, o.y, o.z, o.w));  // a NaN in the plane is its max (common.h nmax_)
     }
   }
   __shared__ float ss[4], sm[4];
   s = wave_sum(s);
-  if (MAX) m = wave_max(m);
+  if (MAX) m = wave_nmax(m);
   const int w = tid >> 6;
   if ((tid & 63) == 0) {
     ss[w] = s;
@@ -167,7 +167,7 @@ __global__ __launch_bounds__(256) void bias_act_stats_kernel(const T* __restrict
   __syncthreads();
   if (tid == 0) {
     psum[bx] = (ss[0] + ss[1]) + (ss[2] + ss[3]);
-    if (MAX) pmax[bx] = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+    if (MAX) pmax[bx] = nmax4_(sm[0], sm[1], sm[2], sm[3]);
   }
 }
 
@@ -364,14 +364,14 @@ __global__ __launch_bounds__(256, 2) void conv1x1_thin_kernel(const float* __res
           if (DUAL && row >= c2lo) out2[(long)b * o2_bs + (long)(row - c2lo) * HW + p] = v;
           if (STATS) {
             ts += v;
-            tm = fmaxf(tm, v);
+            tm = nmax_(tm, v);
           }
         }
         if (STATS) {
 #pragma unroll
           for (int o = 1; o < 16; o <<= 1) {  // the 16 lanes of this lane group hold the row's 64 pixels
             ts += __shfl_xor(ts, o, 64);
-            tm = fmaxf(tm, __shfl_xor(tm, o, 64));
+            tm = nmax_(tm, __shfl_xor(tm, o, 64));
           }
           if (l15 == 0) {
             const long ti = ((long)b * M + row) * ntile + tile;
@@ -396,10 +396,10 @@ __global__ __launch_bounds__(256) void thin_stats_reduce_kernel(const float* __r
   float s = 0.f, m = -INFINITY;
   for (int t = lane; t < ntile; t += 64) {
     s += tsum[plane * ntile + t];
-    if (tmax) m = fmaxf(m, tmax[plane * ntile + t]);
+    if (tmax) m = nmax_(m, tmax[plane * ntile + t]);
   }
   s = wave_sum(s);
-  m = wave_max(m);
+  m = wave_nmax(m);
   for (int k = lane; k < parts; k += 64) {
     psum[plane * parts + k] = k == 0 ? s : 0.f;
     if (pmax) pmax[plane * parts + k] = k == 0 ? m : -INFINITY;
