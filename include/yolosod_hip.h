@@ -406,6 +406,14 @@ void yolosod_debug_set_swin_fused(int on);
  * C = 256 / 4 heads through the kernels that run every matrix product as fp16 two-term splits on the fp16 matrix
  * cores at fp32 accuracy (csrc/swin_x3.hip), 0 through the exact-fp32-MFMA fused kernels. */
 int yolosod_debug_set_swin_x3(int on);
+/* Test hooks (host only, no launch): the route of SwinBlock. yolosod_debug_swin_route: the one yolosod_swin_forward
+ * takes for this shape under the current switches, from the launchers' own conditions - 0 decomposed GEMM path,
+ * 1 fp16-split fused (csrc/swin_x3.hip), 2 exact fused (csrc/swin_fused.hip), 3 exact wide (csrc/swin_wide.hip),
+ * -1 a shape it rejects. yolosod_debug_swin_last_route: the one the last yolosod_swin_forward /
+ * yolosod_swin_forward_prepared call of this process took (-1: none yet), recorded where the launcher reported its
+ * launch. */
+int yolosod_debug_swin_route(int B, int C, int num_heads, int H, int W, int window, int mlp_hidden);
+int yolosod_debug_swin_last_route(void);
 /* The yolosod_debug_set_* switches that return int return the previous state. */
 /* Test hook: pixels per area group of the A2 proj + SiLU + pooling kernel (the launcher takes the fewest area groups
  * whose row bands fit; 208 by default - two workgroups per CU; <= 0 restores 208). Same

@@ -33,6 +33,12 @@ OPS = {
     "swin_c64_h16x12": ("SwinBlock", (64, 2, 7), (1, 64, 16, 12)),
     "swin_c64_h20x5": ("SwinBlock", (64, 2, 7), (1, 64, 20, 5)),
     "swin_c256_h9": ("SwinBlock", (256, 4, 7), (1, 256, 9, 9)),
+    # the fp32 routes besides (64, 2) / (256, 4) at 7x7: the exact fused kernel's other instantiations and the
+    # decomposed GEMM path. "fp32_": no bf16 kernel (bf16 SwinBlock needs C % 64 == 0 and head dim >= 32)
+    "swin_c128_h9x16": ("SwinBlock", (128, 4, 7), (1, 128, 9, 16)),
+    "swin_gemm_c256_h6x5": ("SwinBlock", (256, 4, 7), (2, 256, 6, 5)),
+    "fp32_swin_c64_nh4_h14x9": ("SwinBlock", (64, 4, 7), (1, 64, 14, 9)),
+    "fp32_swin_c96_h9x16": ("SwinBlock", (96, 3, 7), (1, 96, 9, 16)),
     # MambaBlock(c, c_hidden, seq_reduction) (GLU fallback): fusion-v5 L7 is (128, 256, 2) at P3
     "mamba_c128_h16": ("MambaBlock", (128, 256, 2), (1, 128, 16, 16)),
     "mamba_c64_h15x13": ("MambaBlock", (64, 64, 2), (2, 64, 15, 13)),

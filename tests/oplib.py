@@ -18,11 +18,17 @@ def build_fixture_module(name: str, classes: dict | None = None):
     the folded A2 weights can differ by an ulp across host CPUs (BLAS kernel of the fold), which the output
     tolerance absorbs."""
     op, args, shape = recipes.OPS[name]
+    return build_module(op, args, shape[1], recipes.seed_of(name), classes)
+
+
+def build_module(op: str, args, C: int, seed: int, classes: dict | None = None):
+    """(module, sha256 of the recipe parameters before any BN folding) of ``op(*args)`` on C channels, its parameters
+    drawn from ``seed`` (recipes.perturb_)."""
     cls = (classes or {}).get(op) or getattr(M, op)
     m = cls(*args)
     if op == "SE_Block":
-        m._maybe_build(shape[1], None)
-    recipes.perturb_(m, recipes.seed_of(name))
+        m._maybe_build(C, None)
+    recipes.perturb_(m, seed)
     sha = recipes.params_sha256(m)
     if op == "A2_Attn":  # fixtures use the fused Conv form (AutoBackend fuse=True)
         for c in (m.proj, m.out_proj):

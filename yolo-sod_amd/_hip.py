@@ -93,6 +93,8 @@ SIGNATURES = {
     "yolosod_conv3x3_silu_xs": (_i, [_vp, _l, _vp, _l, _vp, _l, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "yolosod_debug_set_swin_fused": (None, [_i]),
     "yolosod_debug_set_swin_x3": (_i, [_i]),
+    "yolosod_debug_swin_route": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "yolosod_debug_swin_last_route": (_i, []),
     "yolosod_debug_set_head_x2": (_i, [_i]),
     "yolosod_debug_set_a2_x2": (_i, [_i]),
     "yolosod_debug_set_gemm_x2": (None, [_i]),
@@ -530,6 +532,25 @@ class exact_fp32_matrix:
             getattr(lib, f)(v)
         _split_convs_off -= 1
         return False
+
+
+SWIN_ROUTES = ("decomposed", "split_fused", "exact_fused", "exact_wide")
+
+
+def swin_route(B, C, num_heads, H, W, window, hid) -> str:
+    """The route SwinBlock takes for this shape under the current switches (yolosod_debug_swin_route, host only): one
+    of SWIN_ROUTES."""
+    r = int(load_library().yolosod_debug_swin_route(int(B), int(C), int(num_heads), int(H), int(W), int(window),
+                                                    int(hid)))
+    if r < 0:
+        raise RuntimeError(f"SwinBlock: shape {B}x{C}x{H}x{W} heads {num_heads} window {window} hidden {hid} unsupported")
+    return SWIN_ROUTES[r]
+
+
+def swin_last_route():
+    """The route the last fp32 SwinBlock launch of this process took (yolosod_debug_swin_last_route; None: none yet)."""
+    r = int(load_library().yolosod_debug_swin_last_route())
+    return None if r < 0 else SWIN_ROUTES[r]
 
 
 def swin_prep_bytes(C, num_heads, hid) -> int:

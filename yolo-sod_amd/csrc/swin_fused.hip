@@ -678,6 +678,14 @@ __global__ __launch_bounds__(256, 3) void swin_fused_kernel(SwinFusedArgs p) {
 
 using namespace ys;
 
+// the shapes yolosod_swin_fused_launch launches (it returns 0 for every other one)
+bool yolosod_swin_fused_takes(int B, int C, int H, int W, int num_heads, int wh, int ww, int nWin, int mlp_hidden) {
+  if (wh * ww > SW_ROWS || wh > 7 || ww > 7 || mlp_hidden != 2 * C) return false;
+  if ((long)C * H * W >= (1L << 30)) return false;  // per-image byte offsets are 32-bit (buffer loads) in the kernel
+  if ((long)B * nWin >= (1L << 31)) return false;    // window indices are 32-bit
+  return (C == 64 || C == 128) && (num_heads == 2 || num_heads == 4);
+}
+
 // returns 1 if launched, 0 if the shape is not handled by the fused kernel, <0 on error
 int yolosod_swin_fused_launch(const float* x, float* y, int B, int C, int H, int W, int num_heads, int wh, int ww,
                               int nWx, int nWin, const float* dw_w, const float* ln1_w, const float* ln1_b,
@@ -687,9 +695,7 @@ int yolosod_swin_fused_launch(const float* x, float* y, int B, int C, int H, int
                               const float* mlp2_b, const float* pw_w, const float* bn_scale, const float* bn_shift,
                               hipStream_t st) {
   const int L = wh * ww;
-  if (L > SW_ROWS || wh > 7 || ww > 7 || mlp_hidden != 2 * C) return 0;
-  if ((long)C * H * W >= (1L << 30)) return 0;  // per-image byte offsets are 32-bit (buffer loads) in the kernel
-  if ((long)B * nWin >= (1L << 31)) return 0;    // window indices are 32-bit
+  if (!yolosod_swin_fused_takes(B, C, H, W, num_heads, wh, ww, nWin, mlp_hidden)) return 0;
   SwinFusedArgs a{x, y, B, H, W, wh, ww, nWx, nWin, L, dw_w, ln1_w, ln1_b, ln1_eps, in_proj_w, in_proj_b,
                   out_proj_w, out_proj_b, ln2_w, ln2_b, ln2_eps, mlp1_w, mlp1_b, mlp2_w, mlp2_b, pw_w,
                   bn_scale, bn_shift, 1.0f / sqrtf((float)(C / num_heads))};

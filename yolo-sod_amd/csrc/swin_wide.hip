@@ -574,6 +574,12 @@ __global__ __launch_bounds__(NT, 1) void swin_wide_kernel(Args p) {
 
 using namespace ys;
 
+// the shapes yolosod_swin_wide_launch launches (it returns 0 for every other one)
+bool yolosod_swin_wide_takes(int B, int C, int H, int W, int num_heads, int wh, int ww, int nWin, int mlp_hidden) {
+  if (C != wide::C || num_heads != C / wide::HD || wh != 7 || ww != 7 || mlp_hidden != 2 * C) return false;
+  return (long)C * H * W < (1L << 30) && (long)B * nWin < (1L << 31);  // 32-bit byte offsets / indices
+}
+
 // returns 1 if launched, 0 if the shape is not handled (C != 256, heads != 4, window != 7x7, hidden != 2C), <0 on
 // error. bn_scale / bn_shift: the pw BatchNorm folded to a per-channel affine (fold_bn_kernel).
 int yolosod_swin_wide_launch(const float* x, float* y, int B, int C, int H, int W, int num_heads, int wh, int ww,
@@ -583,8 +589,7 @@ int yolosod_swin_wide_launch(const float* x, float* y, int B, int C, int H, int 
                              const float* mlp1_w, const float* mlp1_b, int mlp_hidden, const float* mlp2_w,
                              const float* mlp2_b, const float* pw_w, const float* bn_scale, const float* bn_shift,
                              hipStream_t st) {
-  if (C != wide::C || num_heads != C / wide::HD || wh != 7 || ww != 7 || mlp_hidden != 2 * C) return 0;
-  if ((long)C * H * W >= (1L << 30) || (long)B * nWin >= (1L << 31)) return 0;  // 32-bit byte offsets / indices
+  if (!yolosod_swin_wide_takes(B, C, H, W, num_heads, wh, ww, nWin, mlp_hidden)) return 0;
   wide::Args a{x, y, B, H, W, nWx, nWin, dw_w, ln1_w, ln1_b, ln1_eps, in_proj_w, in_proj_b, out_proj_w, out_proj_b,
                ln2_w, ln2_b, ln2_eps, mlp1_w, mlp1_b, mlp2_w, mlp2_b, pw_w, bn_scale, bn_shift,
                1.0f / sqrtf((float)wide::HD)};

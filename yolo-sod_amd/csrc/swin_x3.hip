@@ -1337,6 +1337,12 @@ bool yolosod_swin_x3_ok(int C, int num_heads, int wh, int ww, int mlp_hidden) {
          ((C == 64 && num_heads == 2) || (C == x3::wx::C && num_heads == C / x3::wx::HD));
 }
 
+// the shapes yolosod_swin_x3_run / yolosod_swin_x3_launch launch (they return 0 for every other one)
+bool yolosod_swin_x3_takes(int B, int C, int H, int W, int num_heads, int wh, int ww, int nWin, int mlp_hidden) {
+  if (!yolosod_swin_x3_ok(C, num_heads, wh, ww, mlp_hidden)) return false;
+  return (long)C * H * W < (1L << 30) && (long)B * nWin < (1L << 31);  // 32-bit byte offsets / window indices
+}
+
 size_t yolosod_swin_x3_workspace(int C, int mlp_hidden) {
   Sizer s;
   s.take<h16_t>((size_t)2 * 3 * C * C);            // in_proj planes
@@ -1411,8 +1417,7 @@ int yolosod_swin_x3_run(const float* x, float* y, int B, int C, int H, int W, in
                         int nWin, const float* dw_w, float ln1_eps, const float* out_proj_b, float ln2_eps,
                         int mlp_hidden, const float* mlp2_b, const void* prep, size_t prep_bytes, void* ws,
                         size_t ws_bytes, hipStream_t st) {
-  if (!yolosod_swin_x3_ok(C, num_heads, wh, ww, mlp_hidden)) return 0;
-  if ((long)C * H * W >= (1L << 30) || (long)B * nWin >= (1L << 31)) return 0;
+  if (!yolosod_swin_x3_takes(B, C, H, W, num_heads, wh, ww, nWin, mlp_hidden)) return 0;
   X3Prep q;
   if (!x3_carve(const_cast<void*>(prep), prep_bytes, C, mlp_hidden, q)) {
     set_error("swin_x3: prepared-parameter buffer too small (%zu)", prep_bytes);
@@ -1447,8 +1452,7 @@ int yolosod_swin_x3_launch(const float* x, float* y, int B, int C, int H, int W,
                            const float* mlp2_b, const float* pw_w, const float* bn_w, const float* bn_b,
                            const float* bn_mean, const float* bn_var, float bn_eps, void* workspace,
                            size_t workspace_bytes, hipStream_t st) {
-  if (!yolosod_swin_x3_ok(C, num_heads, wh, ww, mlp_hidden)) return 0;
-  if ((long)C * H * W >= (1L << 30) || (long)B * nWin >= (1L << 31)) return 0;
+  if (!yolosod_swin_x3_takes(B, C, H, W, num_heads, wh, ww, nWin, mlp_hidden)) return 0;
   const size_t pb = yolosod_swin_x3_workspace(C, mlp_hidden);
   if (workspace_bytes < pb) {
     set_error("swin_x3: workspace too small (%zu)", workspace_bytes);

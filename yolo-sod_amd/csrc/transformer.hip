@@ -22,7 +22,8 @@
 namespace ys {
 
 // =================================================================================================
-// LayerNorm over rows of C (token-major), one wave per row. y = (x-mean)*rstd*w + b, biased variance.
+// LayerNorm over rows of C (token-major), one wave per row. y = (x-mean)*rstd*w + b, biased variance. The entry
+// yolosod_layernorm only: the operators normalise through gemm_f32.h's ln_rows / row_stats or inside their fused kernels.
 // =================================================================================================
 template <int VPL>  // values per lane, C <= 64*VPL
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict__ x, float* __restrict__ y, long rows,
@@ -32,15 +33,19 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
   const float* xr = x + row * C;
+  // the mean as x0 + mean(x - x0), x0 the row's first element: a constant row gives x - mean = 0 and y = b exactly,
+  // as torch's Welford mean does (sum(x) / C rounds, and 1 / sqrt(eps) = 316 multiplies what is left of x - mean), and
+  // a row with a large common offset loses no bits of its deviations to the sum
+  const float x0 = xr[0];
   float v[VPL];
   float s = 0.f;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
     const int c = lane + 64 * i;
-    v[i] = (c < C) ? xr[c] : 0.f;
-    s += v[i];
+    v[i] = (c < C) ? xr[c] : x0;
+    s += v[i] - x0;
   }
-  const float mean = wave_sum(s) / (float)C;
+  const float mean = x0 + wave_sum(s) / (float)C;
   float q = 0.f;
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
@@ -599,6 +604,10 @@ int yolosod_swin_wide_launch(const float* x, float* y, int B, int C, int H, int 
                              hipStream_t st);
 
 bool yolosod_swin_x3_ok(int C, int num_heads, int wh, int ww, int mlp_hidden);
+// the launchers' own conditions: the shapes each one launches (every other one returns 0 from it)
+bool yolosod_swin_x3_takes(int B, int C, int H, int W, int num_heads, int wh, int ww, int nWin, int mlp_hidden);
+bool yolosod_swin_fused_takes(int B, int C, int H, int W, int num_heads, int wh, int ww, int nWin, int mlp_hidden);
+bool yolosod_swin_wide_takes(int B, int C, int H, int W, int num_heads, int wh, int ww, int nWin, int mlp_hidden);
 size_t yolosod_swin_x3_workspace(int C, int mlp_hidden);
 size_t yolosod_swin_x3_run_workspace(int B, int C, int H, int W);
 int yolosod_swin_x3_launch(const float* x, float* y, int B, int C, int H, int W, int num_heads, int wh, int ww,
@@ -627,6 +636,33 @@ static bool swin_fused_ok(int C, int heads, int wh, int ww, int mlp_hidden) {
   if (C == 256 && heads == 4) return swin_wide_enabled() && wh == 7 && ww == 7;
   return (C == 64 && (heads == 2 || heads == 4)) || (C == 128 && (heads == 2 || heads == 4));
 }
+
+// Route report. yolosod_swin_forward tries the fp16-split fused kernels (swin_x3.hip), then the exact fused kernel
+// (swin_fused.hip) or the exact wide one (swin_wide.hip), then runs the decomposed GEMM path.
+enum { SWIN_ROUTE_DECOMPOSED = 0, SWIN_ROUTE_SPLIT = 1, SWIN_ROUTE_FUSED = 2, SWIN_ROUTE_WIDE = 3 };
+static int g_swin_last_route = -1;  // written where a launcher reported its launch, not from the prediction below
+
+static int swin_route(int B, int C, int H, int W, int heads, int mlp_hidden, const SwinGeom& g) {
+  if (!swin_fused_ok(C, heads, g.wh, g.ww, mlp_hidden)) return SWIN_ROUTE_DECOMPOSED;
+  if (yolosod_swin_x3_takes(B, C, H, W, heads, g.wh, g.ww, g.nWin, mlp_hidden)) return SWIN_ROUTE_SPLIT;
+  if (C == 256)
+    return yolosod_swin_wide_takes(B, C, H, W, heads, g.wh, g.ww, g.nWin, mlp_hidden) ? SWIN_ROUTE_WIDE
+                                                                                    : SWIN_ROUTE_DECOMPOSED;
+  return yolosod_swin_fused_takes(B, C, H, W, heads, g.wh, g.ww, g.nWin, mlp_hidden) ? SWIN_ROUTE_FUSED
+                                                                                   : SWIN_ROUTE_DECOMPOSED;
+}
+
+// Test hooks (host only, no launch). The route yolosod_swin_forward would take for this shape under the current
+// switches: 0 decomposed GEMM path, 1 fp16-split fused, 2 exact fused, 3 exact wide; -1 for a shape it rejects.
+YS_EXPORT int yolosod_debug_swin_route(int B, int C, int num_heads, int H, int W, int window, int mlp_hidden) {
+  if (B <= 0 || C <= 0 || num_heads <= 0 || H <= 0 || W <= 0 || window <= 0) return -1;
+  if (C % 32 != 0 || mlp_hidden % 32 != 0) return -1;
+  const SwinGeom g = swin_geom(B, H, W, window);
+  if (g.L > 320) return -1;
+  return swin_route(B, C, H, W, num_heads, mlp_hidden, g);
+}
+// The route the last yolosod_swin_forward / yolosod_swin_forward_prepared call of this process took (-1: none yet).
+YS_EXPORT int yolosod_debug_swin_last_route(void) { return g_swin_last_route; }
 
 // =================================================================================================
 // C ABI
@@ -749,6 +785,7 @@ YS_EXPORT int yolosod_swin_forward_prepared(const float* x, float* y, int B, int
     YS_CHECK_ARG(r == 1, "swin_prepared: shape C=%d heads=%d window %dx%d has no prepared-parameter kernel", C,
                  num_heads, g.wh, g.ww);
   }
+  g_swin_last_route = SWIN_ROUTE_SPLIT;
   return 0;
 }
 
@@ -776,7 +813,10 @@ YS_EXPORT int yolosod_swin_forward(const float* x, float* y, int B, int C, int H
                                           mlp1_w, mlp1_b, mlp_hidden, mlp2_w, mlp2_b, pw_w, bn_w, bn_b, bn_mean,
                                           bn_var, bn_eps, workspace, workspace_bytes, st);
     if (rx < 0) return -1;
-    if (rx == 1) return 0;
+    if (rx == 1) {
+      g_swin_last_route = SWIN_ROUTE_SPLIT;
+      return 0;
+    }
     Carver cf(workspace, workspace_bytes);
     float* fold = cf.take<float>((size_t)C * 2);
     YS_CHECK_ARG(fold, "swin: workspace too small (%zu)", workspace_bytes);
@@ -787,8 +827,12 @@ YS_EXPORT int yolosod_swin_forward(const float* x, float* y, int B, int C, int H
                          in_proj_w, in_proj_b, out_proj_w, out_proj_b, ln2_w, ln2_b, ln2_eps, mlp1_w, mlp1_b,
                          mlp_hidden, mlp2_w, mlp2_b, pw_w, fold, fold + C, st);
     if (r < 0) return -1;
-    if (r == 1) return 0;
+    if (r == 1) {
+      g_swin_last_route = C == 256 ? SWIN_ROUTE_WIDE : SWIN_ROUTE_FUSED;
+      return 0;
+    }
   }
+  g_swin_last_route = SWIN_ROUTE_DECOMPOSED;
   Carver cv(workspace, workspace_bytes);
   float* T = cv.take<float>((size_t)g.ntok * C);
   float* U = cv.take<float>((size_t)g.ntok * C);
