@@ -294,6 +294,20 @@ int yolosod_tile_merge_tta(const float* y, int n, int nc, int A, int src_lo, int
  * outside 1..1024, T outside 1..16, a threshold that is <= 0 or not finite. */
 int yolosod_match_predictions(const float* det, const int* counts, int B, int D, const float* labels,
                               const int* label_off, const float* iouv, int T, uint8_t* tp, void* stream);
+/* ConfusionMatrix.process_batch (detect task) over box_iou  ultralytics/utils/metrics.py:326-382, :52-71, for a whole
+ * batch of padded NMS rows in one launch, no host sync (csrc/eval_confusion.hip). det, counts, labels, label_off as
+ * for yolosod_match_predictions. cm: [B][nc+1][nc+1] int32, rows the predicted class, columns the true class, index nc
+ * the background. Per image, in fp32 without FMA contraction and with IEEE division: a row is kept if conf > conf_thr;
+ * iou = inter / (((a_l + a_d) - inter) + 1e-7f) whatever the classes; a kept row's label is the one of its largest
+ * iou > iou_thr (the highest index on a tie); a label goes to the kept row that claims it with the largest iou (the
+ * highest row on a tie). cm[dc][gc] counts the rows that got their label, cm[dc][nc] the other kept rows, cm[nc][gc]
+ * the labels nobody got; dc / gc the fp32 class truncated to int. A row or label whose class is NaN or truncates
+ * outside [0, nc) is counted nowhere (it still takes part in the matching). Every cell of cm is written exactly once
+ * with plain stores, whatever cm held; integer LDS atomics only: deterministic. Refused: a null det / counts /
+ * label_off / cm, B < 1, D outside 1..1024, nc outside 1..100, a threshold that is < 0 or not finite, a pointer that
+ * is not 4-byte aligned. */
+int yolosod_confusion_matrix(const float* det, const int* counts, int B, int D, const float* labels,
+                             const int* label_off, int nc, float conf_thr, float iou_thr, int32_t* cm, void* stream);
 
 /* Conv epilogue for the PyTorch-ROCm backbone convs (not a reference hot-path op; conv.py:37-55 + block.py:343-356
  * + Concat): out[b*out_bstride + c*HW + p] = act(y[b*y_bstride + c*HW + p] + bias[c]) (+ res[...]); act 0 id, 1 SiLU.

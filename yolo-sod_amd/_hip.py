@@ -60,6 +60,7 @@ SIGNATURES = {
     "yolosod_tile_merge": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _f, _vp]),
     "yolosod_tile_merge_tta": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp]),
     "yolosod_match_predictions": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
+    "yolosod_confusion_matrix": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _vp, _vp]),
     "yolosod_tta_views": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "yolosod_tta_merge": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _i, _f, _f, _vp]),
     "yolosod_stem_workspace": (_sz, [_i, _i, _i, _i]),
@@ -1701,6 +1702,62 @@ def match_predictions(out, counts, labels, label_off, iouv=IOU_THRESHOLDS):
                    out.data_ptr(), counts.data_ptr(), B, D, labels.data_ptr() if labels.shape[0] else None,
                    label_off.data_ptr(), thr.ctypes.data, T, tp.data_ptr(), _stream(dev)), "match_predictions")
     return tp
+
+
+EVAL_CONFUSION_LABEL_CHUNK = 256  # labels staged through LDS per pass (csrc/eval_confusion.hip econf::CHUNK)
+EVAL_CONFUSION_MAX_D = 1024       # detection rows per image (one lane each)
+EVAL_CONFUSION_MAX_NC = 100       # classes: the workgroup's LDS matrix is (MAX_NC + 1)^2 int32
+
+
+def confusion_matrix(out, counts, labels, label_off, nc, conf=0.25, iou_thres=0.45):
+    """The confusion matrices of a batch of padded NMS rows against its labels, one launch and no host sync
+    (yolosod_confusion_matrix, the reference's ``ConfusionMatrix.process_batch`` over ``box_iou``): ``out``, ``counts``,
+    ``labels`` and ``label_off`` as for :func:`match_predictions`, ``nc`` the number of classes (1..100), ``conf`` and
+    ``iou_thres`` the two thresholds as the kernel compares them, in fp32 and strictly (finite and >= 0; the
+    ``{None, 0.001} -> 0.25`` rule belongs to ``utils.metrics.ConfusionMatrix``). Returns cm, int32 [B, nc + 1, nc + 1]
+    on ``out``'s device: per image, rows the predicted class, columns the true class, index ``nc`` the background.
+    Rows and labels whose class is NaN or truncates outside [0, nc) are counted nowhere.
+
+    ``label_off`` is read on the device, so that it stays inside ``labels`` is the caller's word; everything else the
+    kernel relies on is checked here first: nothing is launched on arguments that fail."""
+    import math
+    lib = load_library()
+    for t, name, dtype, dim in ((out, "out", torch.float32, 3), (counts, "counts", torch.int32, 1),
+                                (labels, "labels", torch.float32, 2), (label_off, "label_off", torch.int32, 1)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"confusion_matrix: {name}: expected a tensor")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"confusion_matrix: {name}: HIP kernel requires a GPU tensor (got device {t.device}); "
+                               "no CPU fallback")
+        if t.dtype != dtype:
+            raise RuntimeError(f"confusion_matrix: {name}: expected {dtype}, got {t.dtype}")
+        if t.dim() != dim:
+            raise RuntimeError(f"confusion_matrix: {name}: expected {dim} dimensions, got shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"confusion_matrix: {name}: expected a contiguous tensor")
+        if t.device != out.device:
+            raise RuntimeError(f"confusion_matrix: out on {out.device}, {name} on {t.device}")
+    B, D = int(out.shape[0]), int(out.shape[1])
+    if B < 1 or not 1 <= D <= EVAL_CONFUSION_MAX_D or int(out.shape[2]) != 6:
+        raise RuntimeError(f"confusion_matrix: out {tuple(out.shape)} unsupported "
+                           f"([B >= 1, 1..{EVAL_CONFUSION_MAX_D}, 6])")
+    if tuple(counts.shape) != (B,) or tuple(label_off.shape) != (B + 1,):
+        raise RuntimeError(f"confusion_matrix: counts {tuple(counts.shape)} / label_off {tuple(label_off.shape)} do "
+                           f"not match {B} images ([{B}] and [{B + 1}] expected)")
+    if int(labels.shape[1]) != 5:
+        raise RuntimeError(f"confusion_matrix: labels {tuple(labels.shape)} is not [L, 5] (cls, x1, y1, x2, y2)")
+    if isinstance(nc, bool) or not isinstance(nc, int) or not 1 <= nc <= EVAL_CONFUSION_MAX_NC:
+        raise RuntimeError(f"confusion_matrix: nc {nc!r} unsupported (an int in 1..{EVAL_CONFUSION_MAX_NC})")
+    conf, iou_thres = float(conf), float(iou_thres)
+    for v, name in ((conf, "conf"), (iou_thres, "iou_thres")):
+        if not (math.isfinite(v) and 0.0 <= v <= 3.4028234663852886e38):
+            raise RuntimeError(f"confusion_matrix: {name} {v} (finite and >= 0 expected)")
+    dev = out.device
+    cm = torch.empty((B, nc + 1, nc + 1), dtype=torch.int32, device=dev)
+    _check(_launch(("confusion_matrix", (B, D, nc), int(labels.shape[0])), dev, lib.yolosod_confusion_matrix,
+                   out.data_ptr(), counts.data_ptr(), B, D, labels.data_ptr() if labels.shape[0] else None,
+                   label_off.data_ptr(), nc, conf, iou_thres, cm.data_ptr(), _stream(dev)), "confusion_matrix")
+    return cm
 
 
 def gemm_f32(A, B, b_kcontig, bias=None, bias_mode=0, act=0, res=None):

@@ -21,6 +21,8 @@ ARCH = os.environ.get("YOLOSOD_ARCH", "gfx950")
 # indices; the merged boxes are NMS's input), nor the evaluator's box_iou (bit-exact true-positive matrix)
 EXTRA = {"detect.hip": ["-ffp-contract=off"], "nms.hip": ["-ffp-contract=off"],
          "tile_merge.hip": ["-ffp-contract=off"], "eval_match.hip": ["-ffp-contract=off"],
+         # the same box_iou under the confusion matrix's thresholds (bit-exact matrix)
+         "eval_confusion.hip": ["-ffp-contract=off"],
          # the augmented views' bilinear blend and the branch merge: every product and sum rounds on its own
          "tta.hip": ["-ffp-contract=off"],
          # both of the above in one pass: bit-identical to the two launches only if nothing is contracted here either

@@ -4,6 +4,7 @@ Restates the reference's evaluation arithmetic so GPU detections and CPU-referen
 way (quitedob/yolo-sod = Ultralytics 8.3.63):
   box_iou            ultralytics/utils/metrics.py:52-71     (fp32, eps 1e-7, torchvision formula)
   match_predictions  ultralytics/engine/validator.py:222-262 (greedy, use_scipy=False path)
+  ConfusionMatrix    ultralytics/utils/metrics.py:294-393   (detect task: process_batch, tp_fp)
   smooth             ultralytics/utils/metrics.py:447-452
   compute_ap         ultralytics/utils/metrics.py:505-533   (101-point COCO interpolation)
   ap_per_class       ultralytics/utils/metrics.py:536-622   (max-F1 operating point)
@@ -51,6 +52,66 @@ def match_predictions(pred_classes: torch.Tensor, true_classes: torch.Tensor, io
             pairs = pairs[np.unique(pairs[:, 0], return_index=True)[1]]
         correct[pairs[:, 1].astype(int), ti] = True
     return correct
+
+
+class ConfusionMatrix:
+    """The detect task's confusion matrix on the host, the reference's steps one by one (``where``, ``argsort``,
+    ``np.unique`` twice). ``matrix`` is float64 [nc + 1, nc + 1]: rows the predicted class, columns the true class,
+    index ``nc`` the background. No plots, no normalisation, no classify task.
+
+    Classes are used as indices the way the reference uses them: one outside [0, nc) raises an IndexError or, if
+    negative, wraps. The device path (``_hip.confusion_matrix``) counts such rows and labels nowhere instead."""
+
+    def __init__(self, nc: int, conf=0.25, iou_thres: float = 0.45):
+        self.nc = nc
+        self.matrix = np.zeros((nc + 1, nc + 1))
+        self.conf = 0.25 if conf in {None, 0.001} else conf  # the validator's default conf stands for 0.25 here
+        self.iou_thres = iou_thres
+
+    def process_batch(self, detections, gt_bboxes, gt_cls):
+        """One image: ``detections`` [n, 6] (x1, y1, x2, y2, conf, cls) or None, ``gt_bboxes`` [m, 4] xyxy,
+        ``gt_cls`` [m]; host tensors. Rows at or below ``conf`` are dropped first. The (label, row) pairs with IoU above
+        ``iou_thres`` are ranked by IoU twice, as in :func:`match_predictions`: after the first ranking every row keeps
+        its best label, after the second every label keeps its best row. A label with a row counts at [row's class,
+        label's class], a label without at [nc, class], a kept row without a label at [class, nc]."""
+        true_cls = gt_cls.int().numpy()
+        if detections is None:
+            rows, pred_cls = None, np.zeros(0, dtype=np.int32)
+        else:
+            rows = detections[detections[:, 4] > self.conf]
+            pred_cls = rows[:, 5].int().numpy()
+        pairs = np.zeros((0, 2), dtype=np.int64)  # (label, row)
+        if len(true_cls) and len(pred_cls):
+            iou = box_iou(gt_bboxes, rows[:, :4])
+            li, di = torch.where(iou > self.iou_thres)
+            pairs, score = np.stack([li.numpy(), di.numpy()], 1), iou[li, di].numpy()
+            if len(pairs) > 1:
+                for column in (1, 0):  # one pair per row, then one pair per label: the first in IoU order
+                    ranked = score.argsort()[::-1]
+                    pairs, score = pairs[ranked], score[ranked]
+                    first = np.unique(pairs[:, column], return_index=True)[1]
+                    pairs, score = pairs[first], score[first]
+        found = np.zeros(len(true_cls), dtype=bool)
+        found[pairs[:, 0]] = True
+        used = np.zeros(len(pred_cls), dtype=bool)
+        used[pairs[:, 1]] = True
+        np.add.at(self.matrix, (pred_cls[pairs[:, 1]], true_cls[pairs[:, 0]]), 1)
+        np.add.at(self.matrix, (self.nc, true_cls[~found]), 1)
+        np.add.at(self.matrix, (pred_cls[~used], self.nc), 1)
+
+    def add(self, counts):
+        """Add integer matrices counted elsewhere (the device path): [nc + 1, nc + 1] or a stack of them."""
+        counts = np.asarray(counts)
+        if counts.dtype.kind not in "iu" or counts.shape[-2:] != self.matrix.shape:
+            raise ValueError(f"ConfusionMatrix.add: expected integer [..., {self.nc + 1}, {self.nc + 1}], got "
+                             f"{counts.dtype} {counts.shape}")
+        self.matrix += counts.reshape(-1, *self.matrix.shape).sum(0)
+
+    def tp_fp(self):
+        """(true positives, false positives) per class: the diagonal, and what else a class's row holds (its
+        background column included); the background row is left out."""
+        hits = np.diag(self.matrix)[:self.nc].copy()
+        return hits, self.matrix[:self.nc].sum(1) - hits
 
 
 def smooth(y: np.ndarray, f: float = 0.05) -> np.ndarray:
