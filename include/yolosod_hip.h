@@ -224,7 +224,21 @@ int yolosod_nms_merged(float* pred, int B, int nc, int A, float conf_thres, doub
  * more to nearest even), pad_value / 255 elsewhere. Deterministic. */
 int yolosod_letterbox_ingest(const int64_t* desc, int B, void* out, long out_bstride, int out_h, int out_w,
                              int out_bf16, int pad_value, void* stream);
-/* DetectionPredictor.postprocess -> scale_boxes   ultralytics/models/yolo/detect/predict.py:23-41,
+/* The same front door for decoded video (the project's own: the reference reads BGR frames only): NV12 surfaces -> the
+ * input tensor, one launch per batch (csrc/ingest_nv12.hip). desc: device int64 [B][12] per frame =
+ *   0 Y address of the view's first pixel, 1 UV address of that pixel's chroma pair (row y0 >> 1, pair x0 >> 1 of the
+ *   surface), 2 h, 3 w of the view (1..16384, odd extents allowed), 4 Y pitch, 5 UV pitch in bytes, 6 new_h, 7 new_w,
+ *   8 top, 9 left, 10 the parities of the view's origin on its surface (y0 & 1) << 1 | (x0 & 1), 11 matrix id:
+ *   0 bt601, 1 bt709 (limited range), 2 bt601_full, 3 bt709_full.
+ * View pixel (r, c) takes Y[r][c] and the pair U, V at chroma row (r + py) >> 1, pair (c + px) >> 1 from field 1 (no
+ * chroma interpolation) and becomes uint8 B, G, R in int32 arithmetic (the table and formula are in
+ * csrc/ingest_nv12.hip); those pixels then take yolosod_letterbox_ingest's resize, border, / 255 and bf16 rounding:
+ * the result is bit-equal to yolosod_letterbox_ingest on the converted frames. A frame with h < 1 or w < 1 is not
+ * read: its image is all border. The kernel reads whole aligned dwords that hold a byte of the view's Y rows or of
+ * their chroma pairs. out and the remaining arguments as yolosod_letterbox_ingest. Deterministic. */
+int yolosod_letterbox_ingest_nv12(const int64_t* desc, int B, void* out, long out_bstride, int out_h, int out_w,
+                                  int out_bf16, int pad_value, void* stream);
+/* DetectionPredictor.postprocess -> scale_boxes  ultralytics/models/yolo/detect/predict.py:23-41,
  * ultralytics/utils/ops.py:92-128 (clip_boxes :319-338) on the padded NMS output with per-image geometry, no host
  * sync. det: [B][D][6]; geom: device float [B][5] = gain, pad_x, pad_y, w0, h0. Rows < counts[b]: columns 0..3
  * become (v - pad) / gain (IEEE division) clamped to [0, w0] / [0, h0]; rows >= counts[b] and columns 4, 5 are not

@@ -7,6 +7,7 @@ Hot path (hand-written HIP, ``csrc/``, C ABI in ``include/yolosod_hip.h``): the 
 A2_Attn / SwinBlock, the Detect decode and batched class-wise NMS. Backbone/neck convolutions stay PyTorch-ROCm.
 """
 from . import _hip  # noqa: F401
+from .data.nv12 import NV12Frame  # noqa: F401
 from .nn.tasks import DetectionModel, build_model, parse_model, yaml_model_load  # noqa: F401
 from .utils.ops import non_max_suppression, non_max_suppression_padded  # noqa: F401
 

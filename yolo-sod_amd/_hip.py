@@ -56,6 +56,7 @@ SIGNATURES = {
     "yolosod_bias_act": (_i, [_vp, _l, _vp, _l, _vp, _vp, _l, _i, _i, _l, _i, _vp]),
     "yolosod_upsample2x": (_i, [_vp, _vp, _l, _i, _i, _i, _i, _i, _vp]),
     "yolosod_letterbox_ingest": (_i, [_vp, _i, _vp, _l, _i, _i, _i, _i, _vp]),
+    "yolosod_letterbox_ingest_nv12": (_i, [_vp, _i, _vp, _l, _i, _i, _i, _i, _vp]),
     "yolosod_scale_boxes": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "yolosod_tile_merge": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _i, _i, _f, _vp]),
     "yolosod_tile_merge_tta": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp]),
@@ -1347,6 +1348,89 @@ def letterbox_ingest(images, out_shape, geoms, dtype=torch.float32, out=None, pa
     _check(_launch(key, dev, lib.yolosod_letterbox_ingest, desc.data_ptr(), B, out.data_ptr(), out.stride(0) if B > 1
                    else 3 * out_h * out_w, out_h, out_w, int(dtype == _BF16), int(pad_value), _stream(dev)),
            "letterbox_ingest")
+    return out
+
+
+def letterbox_ingest_nv12(frames, out_shape, geoms, dtype=torch.float32, out=None, pad_value=114):
+    """NV12 frames -> the model's input tensor in one launch (yolosod_letterbox_ingest_nv12): ``frames`` is a sequence
+    of :class:`~yolosod_amd.data.nv12.NV12Frame` on the GPU (sizes and matrices may differ; a crop at any origin with
+    any extents is fine: element stride 1 in ``y``, pixel stride 2 and channel stride 1 in ``uv``, any row pitches).
+    ``geoms``, ``out_shape``, ``dtype``, ``out`` and ``pad_value`` as :func:`letterbox_ingest`. The result is bit-equal
+    to :func:`letterbox_ingest` on the frames converted to uint8 BGR by the integer definition in ``data/nv12.py``.
+
+    The descriptor the kernel reads is built here from each tensor's own ``data_ptr()``, shape and strides only, and
+    everything the kernel relies on is checked here: nothing is launched on a frame that fails."""
+    from .data.nv12 import NV12_MATRICES, NV12Frame
+    lib = load_library()
+    B = len(frames)
+    out_h, out_w = int(out_shape[0]), int(out_shape[1])
+    if B < 1 or len(geoms) != B:
+        raise RuntimeError(f"letterbox_ingest_nv12: {B} frames with {len(geoms)} geometries")
+    if dtype not in (torch.float32, _BF16):
+        raise RuntimeError(f"letterbox_ingest_nv12: output dtype must be float32 or bfloat16, got {dtype}")
+    if out_w % 4 or not (0 < out_h <= INGEST_MAX_DIM and 0 < out_w <= INGEST_MAX_DIM):
+        raise RuntimeError(f"letterbox_ingest_nv12: canvas {out_h}x{out_w} unsupported (width % 4 == 0, "
+                           f"<= {INGEST_MAX_DIM})")
+    rows = []
+    dev = None
+    for i, (f, g) in enumerate(zip(frames, geoms)):
+        if not isinstance(f, NV12Frame):
+            raise TypeError(f"letterbox_ingest_nv12: frame {i}: expected an NV12Frame, got {type(f).__name__}")
+        y, uv = f.y, f.uv
+        py, px = f.parity
+        if y.dtype != torch.uint8 or uv.dtype != torch.uint8:
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: expected uint8 planes, got {y.dtype} / {uv.dtype}")
+        if y.dim() != 2 or uv.dim() != 3 or uv.shape[2] != 2:
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: expected y [h, w] and uv [h/2, w/2, 2], got "
+                               f"{tuple(y.shape)} / {tuple(uv.shape)}")
+        h, w = int(y.shape[0]), int(y.shape[1])
+        if not (0 < h <= INGEST_MAX_DIM and 0 < w <= INGEST_MAX_DIM):
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: {h}x{w} outside 1..{INGEST_MAX_DIM}")
+        ch, cw = ((h - 1 + py) >> 1) + 1, ((w - 1 + px) >> 1) + 1  # chroma rows / pairs the view's pixels name
+        if py not in (0, 1) or px not in (0, 1) or tuple(uv.shape[:2]) != (ch, cw):
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: uv {tuple(uv.shape)} is not the [{ch}, {cw}, 2] of a "
+                               f"{h}x{w} view with origin parity ({py}, {px})")
+        if f.matrix not in NV12_MATRICES:
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: unknown matrix {f.matrix!r}")
+        if w > 1 and y.stride(1) != 1:
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: y element stride {y.stride(1)} (1 expected)")
+        if uv.stride(2) != 1:
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: uv channel stride {uv.stride(2)} (1 expected)")
+        if cw > 1 and uv.stride(1) != 2:
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: uv pixel stride {uv.stride(1)} (2 expected)")
+        ypitch = int(y.stride(0)) if h > 1 else w
+        uvpitch = int(uv.stride(0)) if ch > 1 else 2 * cw
+        if ypitch < w:
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: y row pitch {ypitch} < {w}")
+        if uvpitch < 2 * cw:
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: uv row pitch {uvpitch} < 2 * {cw}")
+        if y.device.type != "cuda" or uv.device.type != "cuda":
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: HIP kernel requires GPU tensors (got devices "
+                               f"{y.device} / {uv.device}); no CPU fallback")
+        if uv.device != y.device:
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: y on {y.device}, uv on {uv.device}")
+        if dev is None:
+            dev = y.device
+        elif y.device != dev:
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i} on {y.device}, frame 0 on {dev}")
+        nh, nw, top, left = (int(v) for v in g[:4])
+        if nh < 1 or nw < 1 or top < 0 or left < 0 or top + nh > out_h or left + nw > out_w:
+            raise RuntimeError(f"letterbox_ingest_nv12: frame {i}: geometry {tuple(g)} leaves the {out_h}x{out_w} "
+                               "canvas")
+        rows.append([y.data_ptr(), uv.data_ptr(), h, w, ypitch, uvpitch, nh, nw, top, left, (py << 1) | px,
+                     NV12_MATRICES.index(f.matrix)])
+    if out is None:
+        out = torch.empty((B, 3, out_h, out_w), dtype=dtype, device=dev)
+    elif (out.dtype != dtype or out.device != dev or tuple(out.shape) != (B, 3, out_h, out_w)
+          or out.stride()[1:] != (out_h * out_w, out_w, 1) or out.stride(0) % 4 or out.stride(0) < 3 * out_h * out_w
+          or out.data_ptr() % 16):
+        raise RuntimeError(f"letterbox_ingest_nv12: out must be a {dtype} [{B}, 3, {out_h}, {out_w}] tensor on {dev} "
+                           "with contiguous 16-byte aligned images and a batch stride that is a multiple of 4")
+    desc = torch.tensor(rows, dtype=torch.int64).pin_memory().to(dev, non_blocking=True)
+    key = ("ingest_nv12", (B, 3, out_h, out_w), 2 if dtype == _BF16 else None)
+    _check(_launch(key, dev, lib.yolosod_letterbox_ingest_nv12, desc.data_ptr(), B, out.data_ptr(), out.stride(0)
+                   if B > 1 else 3 * out_h * out_w, out_h, out_w, int(dtype == _BF16), int(pad_value), _stream(dev)),
+           "letterbox_ingest_nv12")
     return out
 
 

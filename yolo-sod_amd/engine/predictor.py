@@ -25,6 +25,7 @@ import torch.distributed as dist
 
 from .. import _hip
 from ..data.augment import LetterBox
+from ..data.nv12 import NV12Frame
 from ..data.slicing import SlicePlan
 from ..utils import ops
 
@@ -51,9 +52,18 @@ class Ingested:
 def frames_to_device(frames, device, who="DetectionPredictor"):
     """A list of uint8 HWC BGR frames (numpy arrays or torch tensors, on the CPU or on the GPU, any sizes) as a list of
     uint8 [h, w, 3] tensors on the GPU. CPU frames go up as they are: packed into one pinned staging buffer (16-byte
-    aligned slots), one H2D copy, no host sync; GPU frames pass through untouched."""
+    aligned slots), one H2D copy, no host sync; GPU frames pass through untouched.
+
+    A list of :class:`NV12Frame` goes up the same way (:func:`_nv12_to_device`) and comes back as a list of NV12Frame
+    on the GPU; a list that mixes the two kinds is refused."""
     if len(frames) == 0:
         raise ValueError(f"{who}: empty list of frames")
+    nv12 = [isinstance(f, NV12Frame) for f in frames]
+    if any(nv12):
+        if not all(nv12):
+            raise TypeError(f"{who}: the list mixes BGR arrays and NV12Frame (frame {nv12.index(False)} is no "
+                            "NV12Frame); one kind per call")
+        return _nv12_to_device(frames, device)
     ts = []
     for i, f in enumerate(frames):
         if not isinstance(f, torch.Tensor):
@@ -79,6 +89,27 @@ def frames_to_device(frames, device, who="DetectionPredictor"):
         for i, o in zip(host, offs):
             ts[i] = up[o:o + ts[i].numel()].view(ts[i].shape)
     return ts
+
+
+def _nv12_to_device(frames, device):
+    """NV12 frames on the GPU: the planes of CPU frames packed into one pinned staging buffer (16-byte aligned slots,
+    every plane contiguous there), one H2D copy, no host sync; a frame whose planes are on the GPU passes through."""
+    device = torch.device(device)
+    planes = [(i, k, p) for i, f in enumerate(frames) for k, p in enumerate((f.y, f.uv)) if p.device.type == "cpu"]
+    up = {}
+    if planes:
+        offs, total = [], 0
+        for _, _, p in planes:
+            offs.append(total)
+            total += (p.numel() + 15) // 16 * 16
+        stage = torch.empty(total, dtype=torch.uint8).pin_memory()
+        for (_, _, p), o in zip(planes, offs):
+            stage[o:o + p.numel()].view(p.shape).copy_(p)
+        dev = stage.to(device, non_blocking=True)
+        for (i, k, p), o in zip(planes, offs):
+            up[i, k] = dev[o:o + p.numel()].view(p.shape)
+    return [NV12Frame._view(up.get((i, 0), f.y), up.get((i, 1), f.uv), f.matrix, f.parity)
+            for i, f in enumerate(frames)]
 
 
 class DetectionPredictor:
@@ -117,8 +148,10 @@ class DetectionPredictor:
         arrays or torch tensors, on the CPU or on the GPU, any sizes): LetterBox, BGR -> RGB, HWC -> CHW, the model's
         dtype, / 255 - as one HIP launch on the raw bytes (``_hip.letterbox_ingest``). CPU frames go up as they are:
         packed into one pinned buffer, one H2D copy, no host resize. Everything else here is arithmetic on shapes:
-        no host sync."""
+        no host sync. A list of :class:`NV12Frame` (decoded video) takes the same path through
+        ``_hip.letterbox_ingest_nv12``: the colour conversion is part of that launch, everything else is shared."""
         ts = frames_to_device(frames, self.device, "DetectionPredictor")
+        nv12 = isinstance(ts[0], NV12Frame)
         shapes = [(int(t.shape[0]), int(t.shape[1])) for t in ts]
         same = all(s == shapes[0] for s in shapes)
         auto = same if self.rect is None else bool(self.rect)
@@ -127,7 +160,8 @@ class DetectionPredictor:
         lb = LetterBox(self.imgsz, auto=auto, stride=self.stride)
         geoms = [lb.geometry(s) for s in shapes]
         canvas = geoms[0][4:]
-        x = _hip.letterbox_ingest(ts, canvas, geoms, self.dtype, pad_value=lb.pad_value)
+        ingest = _hip.letterbox_ingest_nv12 if nv12 else _hip.letterbox_ingest
+        x = ingest(ts, canvas, geoms, self.dtype, pad_value=lb.pad_value)
         # scale_boxes' own gain / pad (ratio_pad=None, ops.py:92-105), recomputed from the two shapes as it does
         rows = []
         for h0, w0 in shapes:
@@ -214,7 +248,8 @@ class SlicedPredictor:
     is cut into overlapping ``slice`` tiles at native resolution (``data/slicing.py``), the model runs on the tiles and,
     with ``full_frame``, on the whole frame too, and all candidates of a frame meet in ONE NMS in frame pixels.
 
-    Takes a list of uint8 HWC BGR frames (numpy arrays, CPU or GPU tensors, any sizes). Stages, each a method so that a
+    Takes a list of uint8 HWC BGR frames (numpy arrays, CPU or GPU tensors, any sizes) or a list of :class:`NV12Frame`
+    (a tile is then ``frame.crop(*rect)``, ingested by ``_hip.letterbox_ingest_nv12``; all else is the same). Stages, each a method so that a
     test or a validator can check it on the same tensors: :meth:`plan` (host arithmetic) -> :meth:`forward_tiles`
     (tiles are views of the device frames, letterboxed onto the one canvas by ``_hip.letterbox_ingest`` straight from
     the frame's memory, ``batch`` tiles per model call, tiles of different frames share a call) -> :meth:`merge`
@@ -269,7 +304,7 @@ class SlicedPredictor:
         views = []
         for f, k in plan.order[lo:hi]:
             y0, x0, y1, x1 = plan.slots[f][k].rect
-            views.append(ts[f][y0:y1, x0:x1])
+            views.append(ts[f].crop(y0, x0, y1, x1) if isinstance(ts[f], NV12Frame) else ts[f][y0:y1, x0:x1])
         return views
 
     def ingest_tiles(self, frames, plan, lo=0, hi=None):
@@ -277,8 +312,8 @@ class SlicedPredictor:
         ts = frames_to_device(frames, self.device, "SlicedPredictor")
         hi = len(plan) if hi is None else hi
         geoms = [plan.slots[f][k].geometry for f, k in plan.order[lo:hi]]
-        return _hip.letterbox_ingest(self._views(ts, plan, lo, hi), plan.canvas, geoms, self.dtype,
-                                     pad_value=plan.pad_value)
+        ingest = _hip.letterbox_ingest_nv12 if isinstance(ts[0], NV12Frame) else _hip.letterbox_ingest
+        return ingest(self._views(ts, plan, lo, hi), plan.canvas, geoms, self.dtype, pad_value=plan.pad_value)
 
     def tta_plan(self, plan):
         """The ``TTAPlan`` of the tiles of ``plan`` (``augment=True``): every tile is on the one canvas."""
