@@ -653,6 +653,24 @@ int yolosod_gemm_bf16(const uint16_t* A, long a_bs, int lda, const uint16_t* B, 
                       uint16_t* C, long c_bs, int ldc, int M, int N, int K, int batch, const float* bias,
                       int bias_mode, int act, const uint16_t* res, void* stream);
 int yolosod_attention_bf16(const uint16_t* qkv, uint16_t* out, long n_seq, int L, int C, int heads, void* stream);
+/* Report hooks of the bf16 kernels (host only, no launch). Each prediction is answered by the predicate the launcher
+ * itself calls; each last_* twin is written where the launch happens, from the launched instance's own constants.
+ *  - yolosod_debug_gemm_bf16_tile: the N extent of the bf16 GEMM's workgroup tile for (M, N, batch): 64 (128x64) or 128
+ *    (128x128). _last_tile: of the last bf16 GEMM launch of this process (-1: none yet). _launches(tile): how many
+ *    launches took that tile so far (-1 for a tile other than 64 / 128).
+ *  - yolosod_debug_swin_bf16_route: what yolosod_swin_forward_bf16 runs for this shape under the current switches:
+ *    0 decomposed with the two-kernel token path, 1 decomposed with the tokens + LN1 pass, 2 fused per-window kernel
+ *    with the 2-byte halo layout, 3 fused with the 16-byte chunk layout, -1 a shape it refuses. _last_route: of the
+ *    last yolosod_swin_forward_bf16 call (-1: none yet).
+ *  - yolosod_debug_attention_bf16_form: head dim * 100 + key blocks (of 16) of the window_attn_bf16_kernel instance
+ *    that takes sequences of L tokens, or -1 for a refused shape. _last_form: of the last bf16 attention launch. */
+int yolosod_debug_gemm_bf16_tile(int M, int N, int batch);
+int yolosod_debug_gemm_bf16_last_tile(void);
+long yolosod_debug_gemm_bf16_launches(int tile);
+int yolosod_debug_swin_bf16_route(int B, int C, int num_heads, int H, int W, int window, int mlp_hidden);
+int yolosod_debug_swin_bf16_last_route(void);
+int yolosod_debug_attention_bf16_form(int L, int C, int heads);
+int yolosod_debug_attention_bf16_last_form(void);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,10 @@ def declared():
 def test_header_declares_entry_points():
     names = declared()
     for n in ("yolosod_se_forward", "yolosod_cbam_forward", "yolosod_ca_forward", "yolosod_a2_forward",
-              "yolosod_swin_forward", "yolosod_detect_decode", "yolosod_nms"):
+              "yolosod_swin_forward", "yolosod_detect_decode", "yolosod_nms",
+              "yolosod_debug_gemm_bf16_tile", "yolosod_debug_gemm_bf16_last_tile", "yolosod_debug_gemm_bf16_launches",
+              "yolosod_debug_swin_bf16_route", "yolosod_debug_swin_bf16_last_route",
+              "yolosod_debug_attention_bf16_form", "yolosod_debug_attention_bf16_last_form"):
         assert n in names
 
 

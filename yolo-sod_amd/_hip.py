@@ -160,6 +160,13 @@ SIGNATURES = {
                                         _i, _vp, _i, _vp]),
     "yolosod_gemm_bf16": (_i, [_vp, _l, _i, _vp, _l, _i, _i, _vp, _l, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _vp]),
     "yolosod_attention_bf16": (_i, [_vp, _vp, _l, _i, _i, _i, _vp]),
+    "yolosod_debug_gemm_bf16_tile": (_i, [_i, _i, _i]),
+    "yolosod_debug_gemm_bf16_last_tile": (_i, []),
+    "yolosod_debug_gemm_bf16_launches": (_l, [_i]),
+    "yolosod_debug_swin_bf16_route": (_i, [_i, _i, _i, _i, _i, _i, _i]),
+    "yolosod_debug_swin_bf16_last_route": (_i, []),
+    "yolosod_debug_attention_bf16_form": (_i, [_i, _i, _i]),
+    "yolosod_debug_attention_bf16_last_form": (_i, []),
 }
 
 _LIB = None
@@ -1872,17 +1879,72 @@ def attention(qkv, n_seq, L, C, heads):
     return out
 
 
-def gemm_bf16(A, B, b_kcontig, bias=None, bias_mode=0, act=0, res=None):
-    """Test hook: A [M,K] bf16; B [N,K] (b_kcontig) or [K,N] bf16; returns C [M,N] bf16 (fp32 accumulation)."""
+def gemm_bf16(A, B, b_kcontig, bias=None, bias_mode=0, act=0, res=None, batch=None):
+    """Test hook: A [M,K] bf16; B [N,K] (b_kcontig) or [K,N] bf16; returns C [M,N] bf16 (fp32 accumulation).
+    ``batch``: B [batch,N,K] / [batch,K,N] and res [batch,M,N] with batch strides b_bs / c_bs, A either shared [M,K]
+    (a_bs = 0, as A2_Attn's weight) or [batch,M,K]; returns C [batch,M,N]. bias_mode 1: bias [M], 2: bias [N]."""
     lib = load_library()
-    M, K = A.shape
-    N = B.shape[0] if b_kcontig else B.shape[1]
-    C = torch.empty((M, N), dtype=_BF16, device=A.device)
-    _check(_launch(("gemm_bf16", (M, N, K), None), A.device, lib.yolosod_gemm_bf16, _dev(A, "A", _BF16), 0, K,
-                   _dev(B, "B", _BF16), 0, B.shape[1], int(b_kcontig), _dev(C, "C", _BF16), 0, N, M, N, K, 1,
-                   None if bias is None else _dev(bias, "bias"), bias_mode, act,
+    M, K = A.shape[-2:]
+    nb = 1 if batch is None else int(batch)
+    Bm = B.shape[-2:]
+    N = Bm[0] if b_kcontig else Bm[1]
+    if batch is not None and (B.dim() != 3 or B.shape[0] != nb or A.dim() not in (2, 3)
+                              or (A.dim() == 3 and A.shape[0] != nb) or (res is not None and res.shape != (nb, M, N))):
+        raise RuntimeError("gemm_bf16: batched operands must be [batch, ...]")
+    C = torch.empty((M, N) if batch is None else (nb, M, N), dtype=_BF16, device=A.device)
+    a_bs = M * K if A.dim() == 3 else 0
+    b_bs, c_bs = (0, 0) if batch is None else (Bm[0] * Bm[1], M * N)
+    _check(_launch(("gemm_bf16", (M, N, K), None if batch is None else nb), A.device, lib.yolosod_gemm_bf16,
+                   _dev(A, "A", _BF16), a_bs, K, _dev(B, "B", _BF16), b_bs, Bm[1], int(b_kcontig), _dev(C, "C", _BF16),
+                   c_bs, N, M, N, K, nb, None if bias is None else _dev(bias, "bias"), bias_mode, act,
                    None if res is None else _dev(res, "res", _BF16), _stream(A.device)), "gemm_bf16")
     return C
+
+
+def gemm_bf16_tile(M, N, batch=1) -> int:
+    """The N extent (64 or 128) of the tile the bf16 GEMM takes for (M, N, batch) (yolosod_debug_gemm_bf16_tile)."""
+    return int(load_library().yolosod_debug_gemm_bf16_tile(int(M), int(N), int(batch)))
+
+
+def gemm_bf16_last_tile():
+    """The tile of the last bf16 GEMM launch of this process (None: none yet)."""
+    r = int(load_library().yolosod_debug_gemm_bf16_last_tile())
+    return None if r < 0 else r
+
+
+def gemm_bf16_launches() -> dict:
+    """bf16 GEMM launches of this process per tile: {64: n, 128: n}."""
+    lib = load_library()
+    return {t: int(lib.yolosod_debug_gemm_bf16_launches(t)) for t in (64, 128)}
+
+
+SWIN_BF16_ROUTES = ("decomposed_tok2", "decomposed_tokln", "fused_2byte", "fused_chunked")
+
+
+def swin_bf16_route(B, C, num_heads, H, W, window, hid):
+    """What the bf16 SwinBlock runs for this shape under the current switches (yolosod_debug_swin_bf16_route, host
+    only): one of SWIN_BF16_ROUTES, or None for a shape it refuses."""
+    r = int(load_library().yolosod_debug_swin_bf16_route(int(B), int(C), int(num_heads), int(H), int(W), int(window),
+                                                         int(hid)))
+    return None if r < 0 else SWIN_BF16_ROUTES[r]
+
+
+def swin_bf16_last_route():
+    """The route of the last bf16 SwinBlock launch of this process (None: none yet)."""
+    r = int(load_library().yolosod_debug_swin_bf16_last_route())
+    return None if r < 0 else SWIN_BF16_ROUTES[r]
+
+
+def attention_bf16_form(L, C, heads):
+    """(head dim, key blocks) of the bf16 attention kernel instance for sequences of L tokens, None if refused."""
+    r = int(load_library().yolosod_debug_attention_bf16_form(int(L), int(C), int(heads)))
+    return None if r < 0 else divmod(r, 100)
+
+
+def attention_bf16_last_form():
+    """(head dim, key blocks) of the last bf16 attention launch of this process (None: none yet)."""
+    r = int(load_library().yolosod_debug_attention_bf16_last_form())
+    return None if r < 0 else divmod(r, 100)
 
 
 def attention_bf16(qkv, n_seq, L, C, heads):

@@ -500,6 +500,18 @@ __global__ __launch_bounds__(256, A_LN ? 2 : 3) void gemm_bf16_kernel(GemmB g) {
 
 static inline bool al_b(const void* p, int bytes) { return ((uintptr_t)p & (bytes - 1)) == 0; }
 
+// The tile rule of launch_gemm_bf16 (and of the report hook yolosod_debug_gemm_bf16_tile): the N extent of the
+// workgroup tile, 64 (128x64 tiles) when N is narrow or 128x128 tiles would leave CUs idle, 128 otherwise.
+static inline int gemm_bf16_tile(int M, int N, int batch) {
+  const long t128 = (long)((M + 127) / 128) * ((N + 127) / 128) * batch;
+  constexpr int force = 0;  // A/B builds: 1 = 128x64 everywhere, 2 = 128x128 everywhere
+  return (force == 1 || (force != 2 && (N <= 64 || t128 < 512))) ? 64 : 128;
+}
+// Report hooks: the tile of the last launch and the launches per tile of this process, written from the launched
+// instantiation's own constants (not from gemm_bf16_tile).
+inline int g_gemm_bf16_last_tile = -1;
+inline long g_gemm_bf16_launches[2] = {0, 0};  // [0]: 128x64, [1]: 128x128
+
 static inline int launch_gemm_bf16(const GemmB& g0, int batch, bool b_kc, hipStream_t st) {
   GemmB g = g0;
   YS_CHECK_ARG(g.K % 64 == 0, "gemm_bf16: K=%d must be a multiple of 64", g.K);
@@ -528,12 +540,11 @@ static inline int launch_gemm_bf16(const GemmB& g0, int batch, bool b_kc, hipStr
     } else {                                                                                                    \
       hipLaunchKernelGGL((gemm_bf16_kernel<WM_, WN_, MI_, NI_, false, false>), grid, dim3(256), 0, st, g);      \
     }                                                                                                           \
+    g_gemm_bf16_last_tile = bn;                                                                                 \
+    ++g_gemm_bf16_launches[bn == 128];                                                                          \
   } while (0)
   YS_CHECK_ARG(b_kc || !ln, "gemm_bf16: LN prologue needs a K-contiguous B");
-  // 128x64 tiles when N is narrow or 128x128 would leave CUs idle; 128x128 otherwise
-  const long t128 = (long)((g.M + 127) / 128) * ((g.N + 127) / 128) * batch;
-  constexpr int force = 0;  // A/B builds: 1 = 128x64 everywhere, 2 = 128x128 everywhere
-  if (force == 1 || (force != 2 && (g.N <= 64 || t128 < 512))) YS_GEMMB_LAUNCH(4, 1, 1, 2);
+  if (gemm_bf16_tile(g.M, g.N, batch) == 64) YS_GEMMB_LAUNCH(4, 1, 1, 2);
   else YS_GEMMB_LAUNCH(2, 2, 2, 2);
 #undef YS_GEMMB_LAUNCH
   YS_CHECK_LAUNCH("gemm_bf16");

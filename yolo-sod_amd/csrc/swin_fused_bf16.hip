@@ -627,6 +627,15 @@ bool yolosod_swin_fused_bf16_ok(int C, int num_heads, int wh, int ww, int mlp_hi
          ((C == 128 && (num_heads == 2 || num_heads == 4)) || (C == 64 && num_heads == 2));
 }
 
+// the launcher's own condition (yolosod_swin_forward_bf16 and its route report ask it too)
+bool yolosod_swin_fused_bf16_takes(int B, int C, int num_heads, int wh, int ww, int nWin, int mlp_hidden) {
+  return yolosod_swin_fused_bf16_ok(C, num_heads, wh, ww, mlp_hidden) && (long)B * nWin < (1L << 31);
+}
+// the halo layout swin_fused_bf16_kernel stages with, its uniform branch on W: 16-byte chunks (true) or 2-byte loads
+bool yolosod_swin_fused_bf16_chunked(int W) { return (W & 7) == 0; }
+static int g_last_chunked = 0;  // of the last launch, written there
+int yolosod_swin_fused_bf16_last_chunked(void) { return g_last_chunked; }
+
 // returns 1 if launched, 0 if the shape is not handled (decomposed path), < 0 on error
 int yolosod_swin_fused_bf16_launch(const bf16_t* x, bf16_t* y, int B, int C, int H, int W, int num_heads, int wh,
                                    int ww, int nWx, int nWin, const float* dw_w, const float* ln1_w, const float* ln1_b,
@@ -635,7 +644,7 @@ int yolosod_swin_fused_bf16_launch(const bf16_t* x, bf16_t* y, int B, int C, int
                                    const float* ln2_b, float ln2_eps, const bf16_t* mlp1_w, const float* mlp1_b,
                                    int mlp_hidden, const bf16_t* mlp2_w, const float* mlp2_b, const bf16_t* pw_w,
                                    const float* bn_scale, const float* bn_shift, bf16_t* wfrag, hipStream_t st) {
-  if (!yolosod_swin_fused_bf16_ok(C, num_heads, wh, ww, mlp_hidden) || (long)B * nWin >= (1L << 31)) return 0;
+  if (!yolosod_swin_fused_bf16_takes(B, C, num_heads, wh, ww, nWin, mlp_hidden)) return 0;
   // weight planes in fragment-major order (wfrag: yolosod_swin_fused_bf16_wfrag_elems(C, hid) bf16)
   const int hid = mlp_hidden;
   WFragArgs fa{};
@@ -666,5 +675,6 @@ int yolosod_swin_fused_bf16_launch(const bf16_t* x, bf16_t* y, int B, int C, int
     set_error("swin_fused_bf16: launch failed: %s", hipGetErrorString(e));
     return -1;
   }
+  g_last_chunked = (a.W & 7) == 0;
   return 1;
 }

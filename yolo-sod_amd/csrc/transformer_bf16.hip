@@ -190,22 +190,52 @@ constexpr size_t wattn_lds_bytes() {
   return sizeof(bf16_t) * ((size_t)N * 16 * (HD + 8) + (size_t)N * 16 * (HD + 16) + 64 * (size_t)(N * 16 + 8));
 }
 
+// key-block counts with an instance whose K / V^T / P tiles fit the 160 KiB of LDS
+#define YS_WATTN_ALL YS_WATTN(4) YS_WATTN(6) YS_WATTN(8) YS_WATTN(10) YS_WATTN(12) YS_WATTN(16) YS_WATTN(20)
+
+// the instance (its NKB) that takes nkb key blocks of head dim HD; -1: none compiled
+template <int HD>
+static int wattn_instance(int nkb) {
+#define YS_WATTN(N)                                               \
+  if constexpr (wattn_lds_bytes<HD, N>() <= 160 * 1024) {         \
+    if (nkb <= N) return N;                                       \
+  }
+  YS_WATTN_ALL
+#undef YS_WATTN
+  return -1;
+}
+
+static int wattn_key_blocks(int L) { return ((L + 31) / 32) * 2; }  // blocks of 16, padded to whole 32-key steps
+
+// The kernel form of an attention call, HD * 100 + NKB, or -1 for a shape launch_attention_bf16 refuses: the
+// predicate of the launcher, of the callers' checks ahead of their first launch, and of the report hook.
+static int attention_bf16_form(int L, int C, int heads) {
+  if (heads <= 0 || C <= 0 || C % heads != 0 || C % 8 != 0 || L <= 0 || L > 320) return -1;
+  const int hd = C / heads, nkb = wattn_key_blocks(L);
+  const int n = hd == 32 ? wattn_instance<32>(nkb) : hd == 64 ? wattn_instance<64>(nkb)
+              : hd == 128 ? wattn_instance<128>(nkb) : -1;
+  return n < 0 ? -1 : hd * 100 + n;
+}
+static int g_attn_bf16_last_form = -1;  // written where the launch happens, from the instance's own constants
+
 template <int HD>
 static int launch_wattn_hd(int nkb, dim3 grid, hipStream_t st, const bf16_t* qkv, int C, bf16_t* out,
                            const TokMap& tm, float scale) {
-  // key-block counts with an instance whose K / V^T / P tiles fit the 160 KiB of LDS
+  const int inst = wattn_instance<HD>(nkb);
 #define YS_WATTN(N)                                                                                             \
   if constexpr (wattn_lds_bytes<HD, N>() <= 160 * 1024) {                                                       \
-    if (nkb <= N) {                                                                                             \
+    if (inst == N) {                                                                                            \
       hipLaunchKernelGGL((window_attn_bf16_kernel<HD, N>), grid, dim3(256), 0, st, qkv, C, out, tm, scale);     \
+      g_attn_bf16_last_form = HD * 100 + N;                                                                     \
       return 0;                                                                                                 \
     }                                                                                                           \
   }
-  YS_WATTN(4) YS_WATTN(6) YS_WATTN(8) YS_WATTN(10) YS_WATTN(12) YS_WATTN(16) YS_WATTN(20)
+  YS_WATTN_ALL
 #undef YS_WATTN
   YS_CHECK_ARG(false, "attention_bf16: %d key blocks of head dim %d unsupported", nkb, HD);
   return -1;
 }
+#undef YS_WATTN_ALL
 
 static int launch_attention_bf16(const bf16_t* qkv, bf16_t* out, long n_seq, int C, int heads, const TokMap& tm,
                                  hipStream_t st) {
@@ -215,7 +245,10 @@ static int launch_attention_bf16(const bf16_t* qkv, bf16_t* out, long n_seq, int
   YS_CHECK_ARG(L > 0 && L <= 320, "attention_bf16: sequence length %d unsupported (1..320)", L);
   YS_CHECK_ARG(n_seq < 65536, "attention_bf16: too many sequences (%ld)", n_seq);
   YS_CHECK_ARG(C % 8 == 0, "attention_bf16: C=%d must be a multiple of 8", C);
-  const int nkb = ((L + 31) / 32) * 2;  // key blocks of 16, padded to whole 32-key steps
+  YS_CHECK_ARG(hd == 32 || hd == 64 || hd == 128, "attention_bf16: head dim %d unsupported (32, 64, 128)", hd);
+  YS_CHECK_ARG(attention_bf16_form(L, C, heads) >= 0,
+               "attention_bf16: sequence length %d with head dim %d unsupported (no instance fits LDS)", L, hd);
+  const int nkb = wattn_key_blocks(L);
   const float scale = 1.0f / sqrtf((float)hd);
   dim3 grid((L + 63) / 64, heads, (unsigned)n_seq);
   int rc;
@@ -537,6 +570,9 @@ int yolosod_swin_fused_bf16_launch(const bf16_t* x, bf16_t* y, int B, int C, int
                                    int mlp_hidden, const bf16_t* mlp2_w, const float* mlp2_b, const bf16_t* pw_w,
                                    const float* bn_scale, const float* bn_shift, bf16_t* wfrag, hipStream_t st);
 size_t yolosod_swin_fused_bf16_wfrag_elems(int C, int mlp_hidden);
+bool yolosod_swin_fused_bf16_takes(int B, int C, int num_heads, int wh, int ww, int nWin, int mlp_hidden);
+bool yolosod_swin_fused_bf16_chunked(int W);
+int yolosod_swin_fused_bf16_last_chunked(void);
 
 // =================================================================================================
 // C ABI (bf16 storage: activations / GEMM weights are bf16 bit patterns, other parameters fp32)
@@ -555,8 +591,19 @@ YS_EXPORT int yolosod_gemm_bf16(const bf16_t* A, long a_bs, int lda, const bf16_
   return launch_gemm_bf16(g, batch, b_kcontig != 0, (hipStream_t)stream);
 }
 
-// Test hook: which bf16 GEMM kernel takes the K-contiguous calls (3 / 2: LDS-DMA ring of 3 / 2 buffers, 0: register
-// staged).
+// Test hooks (host only, no launch). yolosod_debug_gemm_bf16_tile: the N extent of the tile launch_gemm_bf16 takes for
+// (M, N, batch), 64 or 128, from the launcher's own rule. yolosod_debug_gemm_bf16_last_tile / _launches(tile): the tile
+// of the last bf16 GEMM launch of this process (-1: none yet) and the launches with that tile so far, both written
+// where the launch happens.
+YS_EXPORT int yolosod_debug_gemm_bf16_tile(int M, int N, int batch) { return gemm_bf16_tile(M, N, batch); }
+YS_EXPORT int yolosod_debug_gemm_bf16_last_tile(void) { return g_gemm_bf16_last_tile; }
+YS_EXPORT long yolosod_debug_gemm_bf16_launches(int tile) {
+  return tile == 64 ? g_gemm_bf16_launches[0] : tile == 128 ? g_gemm_bf16_launches[1] : -1;
+}
+// The attention kernel form for (L, C, heads): head dim * 100 + key blocks of the instance, -1 for a refused shape;
+// and the form of the last attention launch of this process (-1: none yet).
+YS_EXPORT int yolosod_debug_attention_bf16_form(int L, int C, int heads) { return attention_bf16_form(L, C, heads); }
+YS_EXPORT int yolosod_debug_attention_bf16_last_form(void) { return g_attn_bf16_last_form; }
 
 // Test hook: attention over contiguous sequences of L rows of a [n_seq*L][3C] bf16 QKV matrix -> [n_seq*L][C].
 YS_EXPORT int yolosod_attention_bf16(const bf16_t* qkv, bf16_t* out, long n_seq, int L, int C, int heads,
@@ -569,7 +616,7 @@ YS_EXPORT int yolosod_attention_bf16(const bf16_t* qkv, bf16_t* out, long n_seq,
 
 YS_EXPORT size_t yolosod_swin_workspace_bf16(int B, int C, int H, int W, int num_heads, int window, int mlp_hidden) {
   SwinGeomB g = swin_geom_b(B, H, W, window);
-  if (yolosod_swin_fused_bf16_ok(C, num_heads, g.wh, g.ww, mlp_hidden)) {
+  if (yolosod_swin_fused_bf16_takes(B, C, num_heads, g.wh, g.ww, g.nWin, mlp_hidden)) {
     // fused per-window kernel: folded BN and the fragment-major weight copies
     Sizer s;
     s.take<float>((size_t)C * 2);
@@ -597,6 +644,34 @@ YS_EXPORT int yolosod_debug_set_swin_tokln(int on) {
   tokens_ln_mode() = on ? 1 : 0;
   return prev;
 }
+static size_t swin_tokln_lds(int C, int Wp) { return (size_t)Wp * (C + 8) * sizeof(bf16_t); }
+static size_t swin_tok_lds(int Wp) { return (size_t)Wp * 72 * sizeof(bf16_t); }
+// whether the decomposed path takes the tokens + LN1 pass (ln_aligned: ln1_w and ln1_b on 16 bytes)
+static bool swin_tokln_takes(int C, int W, int Wp, bool ln_aligned) {
+  return tokens_ln_env() && W % 8 == 0 && W <= 64 && C <= 1024 && swin_tokln_lds(C, Wp) <= 80 * 1024 && ln_aligned;
+}
+
+// Route report of the bf16 SwinBlock: 0 decomposed with the two-kernel token path, 1 decomposed with the tokens +
+// LN1 pass, 2 fused per-window kernel with the 2-byte halo layout, 3 fused with the 16-byte chunk layout; -1 for a
+// shape yolosod_swin_forward_bf16 refuses. The same predicates the forward calls, in its order.
+enum { SWIN_BF16_TOK2 = 0, SWIN_BF16_TOKLN = 1, SWIN_BF16_FUSED_2B = 2, SWIN_BF16_FUSED_CHUNK = 3 };
+static int g_swin_bf16_last_route = -1;  // written where the launches happen
+static int swin_bf16_route(int B, int C, int heads, int H, int W, int window, int mlp_hidden, bool ln_aligned) {
+  if (B <= 0 || C <= 0 || H <= 0 || W <= 0 || window <= 0 || heads <= 0) return -1;
+  if (C % 64 != 0 || mlp_hidden <= 0 || mlp_hidden % 64 != 0) return -1;
+  const SwinGeomB g = swin_geom_b(B, H, W, window);
+  if (g.L > 320 || g.ntok >= (1L << 31)) return -1;
+  if (yolosod_swin_fused_bf16_takes(B, C, heads, g.wh, g.ww, g.nWin, mlp_hidden))
+    return yolosod_swin_fused_bf16_chunked(W) ? SWIN_BF16_FUSED_CHUNK : SWIN_BF16_FUSED_2B;
+  if (attention_bf16_form(g.L, C, heads) < 0 || (long)B * g.nWin >= 65536) return -1;
+  if (swin_tokln_takes(C, W, g.Wp, ln_aligned)) return SWIN_BF16_TOKLN;
+  return swin_tok_lds(g.Wp) <= 64 * 1024 ? SWIN_BF16_TOK2 : -1;
+}
+YS_EXPORT int yolosod_debug_swin_bf16_route(int B, int C, int num_heads, int H, int W, int window, int mlp_hidden) {
+  return swin_bf16_route(B, C, num_heads, H, W, window, mlp_hidden, true);
+}
+// The route the last yolosod_swin_forward_bf16 call of this process took (-1: none yet).
+YS_EXPORT int yolosod_debug_swin_bf16_last_route(void) { return g_swin_bf16_last_route; }
 
 // SwinBlock.forward (blocks_transformer.py:150-171) on bf16 activations. Weights: in_proj [3C][C], out_proj [C][C],
 // mlp1 [hid][C], mlp2 [C][hid], pw [C][C] bf16; dw [C][9], LN / biases / BN fp32.
@@ -619,7 +694,7 @@ YS_EXPORT int yolosod_swin_forward_bf16(const bf16_t* x, bf16_t* y, int B, int C
   SwinGeomB g = swin_geom_b(B, H, W, window);
   YS_CHECK_ARG(g.L <= 320, "swin_bf16: window of %d tokens unsupported", g.L);
   YS_CHECK_ARG(g.ntok < (1L << 31), "swin_bf16: too many tokens");
-  if (yolosod_swin_fused_bf16_ok(C, num_heads, g.wh, g.ww, mlp_hidden)) {
+  if (yolosod_swin_fused_bf16_takes(B, C, num_heads, g.wh, g.ww, g.nWin, mlp_hidden)) {
     Carver cf(workspace, workspace_bytes);
     float* fold = cf.take<float>((size_t)C * 2);
     bf16_t* wfrag = cf.take<bf16_t>(yolosod_swin_fused_bf16_wfrag_elems(C, mlp_hidden));
@@ -631,8 +706,15 @@ YS_EXPORT int yolosod_swin_forward_bf16(const bf16_t* x, bf16_t* y, int B, int C
                                                  ln2_b, ln2_eps, mlp1_w, mlp1_b, mlp_hidden, mlp2_w, mlp2_b, pw_w, fold,
                                                  fold + C, wfrag, st);
     if (r < 0) return -1;
-    if (r == 1) return 0;
+    if (r == 1) {
+      g_swin_bf16_last_route = yolosod_swin_fused_bf16_last_chunked() ? SWIN_BF16_FUSED_CHUNK : SWIN_BF16_FUSED_2B;
+      return 0;
+    }
   }
+  // the attention's own refusals, ahead of the first launch
+  YS_CHECK_ARG(attention_bf16_form(g.L, C, num_heads) >= 0,
+               "swin_bf16: window of %d tokens with head dim %d/%d unsupported", g.L, C, num_heads);
+  YS_CHECK_ARG((long)B * g.nWin < 65536, "swin_bf16: too many windows (%ld)", (long)B * g.nWin);
   Carver cv(workspace, workspace_bytes);
   bf16_t* T = cv.take<bf16_t>((size_t)g.ntok * C);
   bf16_t* U = cv.take<bf16_t>((size_t)g.ntok * C);
@@ -643,9 +725,8 @@ YS_EXPORT int yolosod_swin_forward_bf16(const bf16_t* x, bf16_t* y, int B, int C
   YS_CHECK_ARG(lns, "swin_bf16: workspace too small (%zu)", workspace_bytes);
   int rc;
   // dwconv + pad -> T (raster tokens), and U = LN1(T) (U is free until the attention writes it)
-  const size_t tokln_lds = (size_t)g.Wp * (C + 8) * sizeof(bf16_t);
-  if (tokens_ln_env() && W % 8 == 0 && W <= 64 && C <= 1024 && tokln_lds <= 80 * 1024 &&
-      ((uintptr_t)ln1_w | (uintptr_t)ln1_b) % 16 == 0) {
+  const size_t tokln_lds = swin_tokln_lds(C, g.Wp);
+  if (swin_tokln_takes(C, W, g.Wp, ((uintptr_t)ln1_w | (uintptr_t)ln1_b) % 16 == 0)) {
     const dim3 grid((unsigned)(B * g.Hp));
     if (C <= 256)
       hipLaunchKernelGGL((swin_tokens_ln_bf16_kernel<1>), grid, dim3(256), tokln_lds, st, x, dw_w, T, U, C, H, W,
@@ -657,12 +738,14 @@ YS_EXPORT int yolosod_swin_forward_bf16(const bf16_t* x, bf16_t* y, int B, int C
       hipLaunchKernelGGL((swin_tokens_ln_bf16_kernel<4>), grid, dim3(256), tokln_lds, st, x, dw_w, T, U, C, H, W,
                          g.Hp, g.Wp, ln1_eps, ln1_w, ln1_b);
     YS_CHECK_LAUNCH("swin_tokens_ln_bf16");
+    g_swin_bf16_last_route = SWIN_BF16_TOKLN;
   } else {
-    const size_t tok_lds = (size_t)g.Wp * 72 * sizeof(bf16_t);
+    const size_t tok_lds = swin_tok_lds(g.Wp);
     YS_CHECK_ARG(tok_lds <= 64 * 1024, "swin_bf16: W=%d too wide for the token kernel", W);
     hipLaunchKernelGGL(swin_tokens_bf16_kernel, dim3((unsigned)(B * g.Hp), (unsigned)((C + 63) / 64)), dim3(256),
                        tok_lds, st, x, dw_w, T, C, H, W, g.Hp, g.Wp);
     YS_CHECK_LAUNCH("swin_tokens_bf16");
+    g_swin_bf16_last_route = SWIN_BF16_TOK2;
     // QKV = LN1(T) Win^T + b_in (LN1(T) -> U once, U is free until the attention writes it)
     if ((rc = launch_ln_rows_bf16(T, C, g.ntok, C, ln1_eps, ln1_w, ln1_b, U, C, st))) return rc;
   }
@@ -732,6 +815,11 @@ YS_EXPORT int yolosod_a2_forward_bf16(const bf16_t* x, bf16_t* y, int B, int C, 
   YS_CHECK_ARG(B >= 0 && C > 0 && H > 0 && W > 0 && num_areas > 0, "a2_bf16: bad shape");
   YS_CHECK_ARG(C % 64 == 0, "a2_bf16: C must be a multiple of 64");
   YS_CHECK_ARG(((long)H * W) % 8 == 0, "a2_bf16: H*W must be a multiple of 8");
+  // the attention's and the pooling kernel's own refusals, ahead of the first launch
+  YS_CHECK_ARG((long)num_areas * W <= 320 && attention_bf16_form(num_areas * W, C, num_heads) >= 0,
+               "a2_bf16: sequence of %ld tokens with head dim %d/%d unsupported", (long)num_areas * W, C, num_heads);
+  YS_CHECK_ARG(B < 65536, "a2_bf16: too many images (%d)", B);
+  YS_CHECK_ARG((size_t)64 * (W + 1) * sizeof(float) <= 64 * 1024, "a2_bf16: W=%d too large for the pooling kernel", W);
   if (B == 0) return 0;
   hipStream_t st = (hipStream_t)stream;
   const int A = num_areas;
@@ -751,7 +839,6 @@ YS_EXPORT int yolosod_a2_forward_bf16(const bf16_t* x, bf16_t* y, int B, int C, 
   ga.epi = epib_plain(XP, C * HW, (int)HW);
   ga.epi.bias = proj_b; ga.epi.bias_mode = 1; ga.epi.act = 1;
   if ((rc = launch_gemm_bf16(ga, B, false, st))) return rc;
-  YS_CHECK_ARG((size_t)64 * (W + 1) * sizeof(float) <= 64 * 1024, "a2_bf16: W=%d too large for the pooling kernel", W);
   hipLaunchKernelGGL(a2_pool_tokens_bf16_kernel, dim3(B * A, (C + 63) / 64), dim3(256),
                      (size_t)64 * (W + 1) * sizeof(float), st, XP, S, C, H, W, A);
   YS_CHECK_LAUNCH("a2_pool_bf16");
