@@ -322,6 +322,32 @@ int yolosod_match_predictions(const float* det, const int* counts, int B, int D,
  * is not 4-byte aligned. */
 int yolosod_confusion_matrix(const float* det, const int* counts, int B, int D, const float* labels,
                              const int* label_off, int nc, float conf_thr, float iou_thr, int32_t* cm, void* stream);
+/* ByteTrack per video stream  ultralytics/trackers/byte_tracker.py:293-405 (BYTETracker.update, bytetrack.yaml), from
+ * device-resident state, one launch per update and no host sync (csrc/track.hip; the definition is
+ * yolo-sod_amd/utils/bytetrack.py). det[b] / counts[b] of every call are the next frame of stream b: padded NMS rows
+ * [B][D][6] = x1, y1, x2, y2, conf, cls and their counts (clamped to 0..D); the row index is the track's idx.
+ * state: B * yolosod_track_state_bytes(T) bytes, 8-byte aligned, owned by the caller and touched only through these
+ * entries: per stream a 64-byte header (int32 frame, next id, overflow), fp64 means [8][T] and covariances [64][T],
+ * int32 state / flags / id / start frame / last frame / idx [T] each, fp32 score / cls [T] each (state: 0 free, 1
+ * Tracked, 2 Lost, 3 Removed but still listed as lost; flags: 1 activated, 2 the id was removed once).
+ * yolosod_track_reset zeroes the state of the n streams listed in streams (device int32, or NULL: all B) and starts
+ * their ids at 1; it must run once before the first update. params: HOST float[8] = track_high_thresh,
+ * track_low_thresh, new_track_thresh, match_thresh, the second (0.5) and unconfirmed (0.7) association thresholds,
+ * max_time_lost (frames), fuse_score (0 / 1); all compared in fp32. tracks: [B][T][8] = x1, y1, x2, y2, track_id,
+ * score, cls, idx per activated tracked track, ascending track_id, rows >= n_tracks[b] zero; n_tracks: [B].
+ * workspace: yolosod_track_workspace(B, T, D) bytes, 16-byte aligned (per stream the association's boxes and its
+ * [T][D] fp32 cost matrix). A birth without a free slot is skipped and counted in the stream's overflow word.
+ * Refused before any launch: a null pointer, B < 1, T not a multiple of 64 in 64..1024, D outside 1..1024, a
+ * workspace that is too small, a parameter that is < 0 or not finite, a misaligned pointer. */
+size_t yolosod_track_state_bytes(int T);
+size_t yolosod_track_workspace(int B, int T, int D);
+int yolosod_track_reset(void* state, int B, int T, const int* streams, int n, void* stream);
+int yolosod_track_update(void* state, int B, int T, const float* det, const int* counts, int D, const float* params,
+                         float* tracks, int* n_tracks, void* workspace, size_t ws_bytes, void* stream);
+/* Test hook (host only): facts of this thread's last yolosod_track_update launch: 0 T, 1 D, 2 B, 3 the workspace
+ * layout (1: track boxes [T], detection boxes [D], cost matrix [T][D] per stream), 4 lanes per workgroup, 5 workspace
+ * bytes per stream; 0 before the first launch, -1 for another what. */
+int yolosod_debug_track_last(int what);
 
 /* Conv epilogue for the PyTorch-ROCm backbone convs (not a reference hot-path op; conv.py:37-55 + block.py:343-356
  * + Concat): out[b*out_bstride + c*HW + p] = act(y[b*y_bstride + c*HW + p] + bias[c]) (+ res[...]); act 0 id, 1 SiLU.

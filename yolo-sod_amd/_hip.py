@@ -62,6 +62,11 @@ SIGNATURES = {
     "yolosod_tile_merge_tta": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp]),
     "yolosod_match_predictions": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "yolosod_confusion_matrix": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i, _f, _f, _vp, _vp]),
+    "yolosod_track_state_bytes": (_sz, [_i]),
+    "yolosod_track_workspace": (_sz, [_i, _i, _i]),
+    "yolosod_track_reset": (_i, [_vp, _i, _i, _vp, _i, _vp]),
+    "yolosod_track_update": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "yolosod_debug_track_last": (_i, [_i]),
     "yolosod_tta_views": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "yolosod_tta_merge": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _i, _f, _f, _vp]),
     "yolosod_stem_workspace": (_sz, [_i, _i, _i, _i]),
@@ -1849,6 +1854,153 @@ def confusion_matrix(out, counts, labels, label_off, nc, conf=0.25, iou_thres=0.
                    out.data_ptr(), counts.data_ptr(), B, D, labels.data_ptr() if labels.shape[0] else None,
                    label_off.data_ptr(), nc, conf, iou_thres, cm.data_ptr(), _stream(dev)), "confusion_matrix")
     return cm
+
+
+TRACK_MAX_T = 1024  # track slots per stream: a multiple of 64 in 64..1024 (csrc/track.hip trk::MAXN)
+TRACK_MAX_D = 1024  # detection rows per stream and frame
+
+
+def track_state_bytes(T: int) -> int:
+    """Bytes of one stream's tracker state for ``T`` slots (yolosod_track_state_bytes)."""
+    return int(load_library().yolosod_track_state_bytes(int(T)))
+
+
+def _track_state_check(what, state, T):
+    if not isinstance(state, torch.Tensor):
+        raise TypeError(f"{what}: state: expected a tensor")
+    if state.device.type != "cuda":
+        raise RuntimeError(f"{what}: state: HIP kernel requires a GPU tensor (got device {state.device}); "
+                           "no CPU fallback")
+    if state.dtype != torch.uint8:
+        raise RuntimeError(f"{what}: state: expected {torch.uint8}, got {state.dtype}")
+    if state.dim() != 2:
+        raise RuntimeError(f"{what}: state: expected 2 dimensions, got shape {tuple(state.shape)}")
+    if not state.is_contiguous():
+        raise RuntimeError(f"{what}: state: expected a contiguous tensor")
+    if isinstance(T, bool) or not isinstance(T, int) or not 64 <= T <= TRACK_MAX_T or T % 64:
+        raise RuntimeError(f"{what}: T {T!r} unsupported (a multiple of 64 in 64..{TRACK_MAX_T})")
+    B = int(state.shape[0])
+    if B < 1 or int(state.shape[1]) != track_state_bytes(T):
+        raise RuntimeError(f"{what}: state {tuple(state.shape)} is not [B >= 1, {track_state_bytes(T)}] for T = {T}")
+    return B
+
+
+def track_reset(state, T, streams=None):
+    """Zero the tracker state of the listed streams (``streams``: an int32 device tensor, or None for all) and start
+    their ids at 1 (yolosod_track_reset); one launch, no host sync. ``state`` is uint8 [B, track_state_bytes(T)]."""
+    lib = load_library()
+    B = _track_state_check("track_reset", state, T)
+    n, sp = 0, None
+    if streams is not None:
+        if not isinstance(streams, torch.Tensor):
+            raise TypeError("track_reset: streams: expected a tensor")
+        if streams.device != state.device:
+            raise RuntimeError(f"track_reset: state on {state.device}, streams on {streams.device}")
+        if streams.dtype != torch.int32:
+            raise RuntimeError(f"track_reset: streams: expected {torch.int32}, got {streams.dtype}")
+        if streams.dim() != 1 or not streams.is_contiguous() or int(streams.shape[0]) > B:
+            raise RuntimeError(f"track_reset: streams {tuple(streams.shape)} is not a contiguous list of at most {B}")
+        n, sp = int(streams.shape[0]), streams.data_ptr()
+        if n == 0:
+            return
+    dev = state.device
+    _check(_launch(("track_reset", (B, T), n), dev, lib.yolosod_track_reset, state.data_ptr(), B, T, sp, n,
+                   _stream(dev)), "track_reset")
+
+
+def track_update(state, T, out, counts, params, tracks=None, n_tracks=None, workspace=None):
+    """One ByteTrack update of every stream, one launch and no host sync (yolosod_track_update; the reference's
+    ``BYTETracker.update`` per stream): ``state`` uint8 [B, track_state_bytes(T)] (reset once with
+    :func:`track_reset`), ``out`` fp32 [B, D, 6] and ``counts`` int32 [B] the padded NMS rows of each stream's next
+    frame, ``params`` a host sequence of 8 floats (``utils.bytetrack.params_vector``). Returns (tracks fp32 [B, T, 8] =
+    x1, y1, x2, y2, track_id, score, cls, idx, ascending track_id, zero padded; n_tracks int32 [B]) on ``out``'s device;
+    ``tracks`` / ``n_tracks`` / ``workspace`` may be passed in to be reused.
+
+    Everything the kernel relies on is checked here first: nothing is launched on arguments that fail."""
+    import math
+
+    import numpy as np
+    lib = load_library()
+    B = _track_state_check("track_update", state, T)
+    for t, name, dtype, dim in ((out, "out", torch.float32, 3), (counts, "counts", torch.int32, 1)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"track_update: {name}: expected a tensor")
+        if t.device.type != "cuda":
+            raise RuntimeError(f"track_update: {name}: HIP kernel requires a GPU tensor (got device {t.device}); "
+                               "no CPU fallback")
+        if t.dtype != dtype:
+            raise RuntimeError(f"track_update: {name}: expected {dtype}, got {t.dtype}")
+        if t.dim() != dim:
+            raise RuntimeError(f"track_update: {name}: expected {dim} dimensions, got shape {tuple(t.shape)}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"track_update: {name}: expected a contiguous tensor")
+        if t.device != state.device:
+            raise RuntimeError(f"track_update: state on {state.device}, {name} on {t.device}")
+    D = int(out.shape[1])
+    if int(out.shape[0]) != B or not 1 <= D <= TRACK_MAX_D or int(out.shape[2]) != 6:
+        raise RuntimeError(f"track_update: out {tuple(out.shape)} unsupported ([{B}, 1..{TRACK_MAX_D}, 6] for "
+                           f"{B} streams)")
+    if tuple(counts.shape) != (B,):
+        raise RuntimeError(f"track_update: counts {tuple(counts.shape)} does not match {B} streams ([{B}] expected)")
+    prm = np.ascontiguousarray(params, dtype=np.float32)
+    if prm.shape != (8,) or not all(math.isfinite(float(v)) and float(v) >= 0.0 for v in prm):
+        raise RuntimeError(f"track_update: params {prm!r} (8 finite values >= 0 expected)")
+    dev = state.device
+    if tracks is None:
+        tracks = torch.empty((B, T, 8), dtype=torch.float32, device=dev)
+    if n_tracks is None:
+        n_tracks = torch.empty((B,), dtype=torch.int32, device=dev)
+    need = int(lib.yolosod_track_workspace(B, T, D))
+    if workspace is None:
+        workspace = _workspace(need, dev)
+    for t, name, dtype, shape in ((tracks, "tracks", torch.float32, (B, T, 8)),
+                                  (n_tracks, "n_tracks", torch.int32, (B,)),
+                                  (workspace, "workspace", torch.uint8, None)):
+        if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != dtype or not t.is_contiguous()
+                or (shape is not None and tuple(t.shape) != shape)):
+            raise RuntimeError(f"track_update: {name}: expected a contiguous {dtype} tensor"
+                               + (f" {list(shape)}" if shape else "") + f" on {dev}")
+    if workspace.numel() < need:
+        raise RuntimeError(f"track_update: workspace of {workspace.numel()} bytes, {need} needed")
+    _check(_launch(("track_update", (B, T, D), 0), dev, lib.yolosod_track_update, state.data_ptr(), B, T,
+                   out.data_ptr(), counts.data_ptr(), D, prm.ctypes.data, tracks.data_ptr(), n_tracks.data_ptr(),
+                   workspace.data_ptr(), workspace.numel(), _stream(dev)), "track_update")
+    return tracks, n_tracks
+
+
+def track_last_launch() -> dict:
+    """Host-side facts of the last :func:`track_update` launch of this thread (yolosod_debug_track_last): T, D, B, the
+    workspace layout (1: boxes and the [T, D] fp32 cost matrix per stream), lanes per workgroup, workspace bytes per
+    stream; all 0 before the first launch."""
+    lib = load_library()
+    return {k: int(lib.yolosod_debug_track_last(i))
+            for i, k in enumerate(("T", "D", "B", "layout", "lanes", "workspace_per_stream"))}
+
+
+def track_state_fetch(state, T) -> list:
+    """Debug fetch (a host sync): the tracker state parsed per stream into numpy arrays - ``frame``, ``next_id``,
+    ``overflow`` and per slot ``state`` (0 free, 1 Tracked, 2 Lost, 3 Removed but listed as lost), ``flags`` (1
+    activated, 2 the id was removed once), ``tid``, ``start``, ``last``, ``idx``, ``score``, ``cls``, ``mean`` [T, 8]
+    and ``cov`` [T, 8, 8] (fp64) - plus ``raw``, the stream's bytes."""
+    import numpy as np
+    B = _track_state_check("track_state_fetch", state, T)
+    raw = state.cpu().numpy()
+    res = []
+    for b in range(B):
+        r = np.ascontiguousarray(raw[b])
+        hdr = r[:64].view(np.int32)
+        o = 64
+        mean = r[o:o + 64 * T].view(np.float64).reshape(8, T).T.copy()
+        o += 64 * T
+        cov = r[o:o + 512 * T].view(np.float64).reshape(8, 8, T).transpose(2, 0, 1).copy()
+        o += 512 * T
+        d = dict(frame=int(hdr[0]), next_id=int(hdr[1]), overflow=int(hdr[2]), mean=mean, cov=cov, raw=r)
+        for name, dt in (("state", np.int32), ("flags", np.int32), ("tid", np.int32), ("start", np.int32),
+                         ("last", np.int32), ("idx", np.int32), ("score", np.float32), ("cls", np.float32)):
+            d[name] = r[o:o + 4 * T].view(dt).copy()
+            o += 4 * T
+        res.append(d)
+    return res
 
 
 def gemm_f32(A, B, b_kcontig, bias=None, bias_mode=0, act=0, res=None):

@@ -26,7 +26,9 @@ EXTRA = {"detect.hip": ["-ffp-contract=off"], "nms.hip": ["-ffp-contract=off"],
          # the augmented views' bilinear blend and the branch merge: every product and sum rounds on its own
          "tta.hip": ["-ffp-contract=off"],
          # both of the above in one pass: bit-identical to the two launches only if nothing is contracted here either
-         "tile_merge_tta.hip": ["-ffp-contract=off"]}
+         "tile_merge_tta.hip": ["-ffp-contract=off"],
+         # the tracker's 1 - IoU and fused-score costs round like numpy's (the assignments are compared exactly)
+         "track.hip": ["-ffp-contract=off"]}
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-variable",
           "-Wno-unused-function", f"-I{INCLUDE}", f"-I{CSRC}"]
 

@@ -114,8 +114,10 @@ def _nv12_to_device(frames, device):
 
 class DetectionPredictor:
     def __init__(self, model, conf=0.25, iou=0.7, max_det=300, classes=None, agnostic_nms=False,
-                 multi_label=False, imgsz=640, rect=None, augment=False, merge_nms=False):
+                 multi_label=False, imgsz=640, rect=None, augment=False, merge_nms=False, tracker=None):
         self.model = model
+        # track mode (engine/tracker.py): a ByteTracker whose streams are this predictor's batch; :meth:`track`
+        self.tracker = tracker
         self.conf, self.iou, self.max_det = conf, iou, max_det
         # merge-NMS (ops.non_max_suppression_padded(merge=True)): kept boxes are their clusters' score-weighted means,
         # merged in canvas pixels before the boxes are mapped and clipped; ``n_merged`` [B, max_det] int32 of the last
@@ -232,6 +234,29 @@ class DetectionPredictor:
             _hip.split_range_flag(reset=True, device=self.device)
         return out, counts, index, ing.shapes
 
+    @torch.inference_mode()
+    def track_padded(self, frames):
+        """:meth:`predict_padded`, then the tracker's update on the rows (after ``scale_boxes_padded``: tracks live in
+        each stream's own pixels): (rows [B, T, 8], n_tracks [B], out, counts, index), no host sync. ``frames[i]`` is
+        the next frame of stream ``i``; the batch must be the tracker's ``streams``. The second-tier association only
+        sees detections the NMS lets through: it needs ``conf <= track_low_thresh`` (the reference's track mode has
+        the same trait; the default ``conf`` stays 0.25)."""
+        _require_tracker(self.tracker, len(frames), "DetectionPredictor")
+        out, counts, index = self.predict_padded(frames)
+        rows, n_tracks = self.tracker.update(out, counts)
+        return rows, n_tracks, out, counts, index
+
+    def track(self, frames):
+        """Per stream :class:`~.tracker.Tracked` (boxes [n, 7] = xyxy, id, conf, cls; index; orig_shape); syncs for
+        the per-stream lists."""
+        from .tracker import tracked_lists
+        rows, n_tracks, out, counts, index = self.track_padded(frames)
+        if isinstance(frames, (list, tuple)):
+            shapes = [tuple(int(v) for v in f.shape[:2]) for f in frames]
+        else:
+            shapes = [tuple(frames.shape[2:])] * int(frames.shape[0])
+        return tracked_lists(rows, n_tracks, index, shapes)
+
     def __call__(self, im):
         if isinstance(im, (list, tuple)):
             out, counts, index, shapes = self._predict_list_guarded(im)
@@ -274,8 +299,9 @@ class SlicedPredictor:
 
     def __init__(self, model, slice=640, overlap=0.2, full_frame=True, cut_margin=None, batch=32, conf=0.25, iou=0.7,
                  max_det=300, classes=None, agnostic_nms=False, multi_label=False, imgsz=640, augment=False, scales=None,
-                 flips=None, merge_nms=False):
+                 flips=None, merge_nms=False, tracker=None):
         self.model = model
+        self.tracker = tracker  # track mode, as DetectionPredictor's
         # merge-NMS in frame pixels, before the clip to the frame; ``n_merged`` [F, max_det] int32 of the last batch
         self.merge_nms = bool(merge_nms)
         self.n_merged = None
@@ -463,10 +489,32 @@ class SlicedPredictor:
         kernels (the frames are not uploaded again)."""
         return self._predict_guarded(frames)[0]
 
+    def track_padded(self, frames):
+        """:meth:`predict_padded`, then the tracker's update on the rows in frame pixels: (rows [F, T, 8], n_tracks [F],
+        out, counts, index), no host sync; as ``DetectionPredictor.track_padded`` (``conf <= track_low_thresh`` for a
+        second tier)."""
+        _require_tracker(self.tracker, len(frames), "SlicedPredictor")
+        out, counts, index = self.predict_padded(frames)
+        rows, n_tracks = self.tracker.update(out, counts)
+        return rows, n_tracks, out, counts, index
+
+    def track(self, frames):
+        """Per stream :class:`~.tracker.Tracked`; ``index`` is ``slot * A + anchor`` (:meth:`locate`)."""
+        from .tracker import tracked_lists
+        rows, n_tracks, out, counts, index = self.track_padded(frames)
+        return tracked_lists(rows, n_tracks, index, [tuple(int(v) for v in f.shape[:2]) for f in frames])
+
     def __call__(self, frames):
         (out, counts, index), plan = self._predict_guarded(frames)
         n = counts.cpu().tolist()
         return [Detections(out[i, : n[i]], index[i, : n[i]], plan.shapes[i]) for i in range(len(n))]
+
+
+def _require_tracker(tracker, batch, who):
+    if tracker is None:
+        raise RuntimeError(f"{who}.track: constructed without a tracker (tracker=ByteTracker(streams=...))")
+    if int(batch) != tracker.streams:
+        raise ValueError(f"{who}.track: batch of {int(batch)} frames for a tracker of {tracker.streams} streams")
 
 
 def shard_bounds(n: int, rank: int, world: int):
