@@ -13,9 +13,16 @@ one seed per stream; the detections of every frame are on the device before a cl
 Nothing is asserted about their ratio. ``ids_equal`` says whether both paths gave the same ids on every frame (the
 scenes are not certified: a near-tie may legitimately differ).
 
-It runs from a checkout: the scenes are the test helper's (tests/bytetrack_ref.py), so that directory goes on sys.path.
+``--tracker botsort`` times BotSortTracker / BotSortTrackerHost (the XYWH filter and the camera-motion phase, DESIGN
+section 35) on the same workload seen through a moving camera: every stream's scene goes through a seeded camera walk
+(tests/botsort_ref.camera_scene: translation up to +-12 px, rotation up to 0.5 degrees, scale 1 +- 0.01 per frame) and
+every update is given the 32 frame-to-frame warps, on the device before a clock starts (fp64 [32, 2, 3]; the first
+frame's are the identity).
 
-  python scripts/bench_track.py [--passes 5] [--out profiles/track_bench_mi355x.json]"""
+It runs from a checkout: the scenes are the test helpers' (tests/bytetrack_ref.py, tests/botsort_ref.py), so that
+directory goes on sys.path.
+
+  python scripts/bench_track.py [--tracker bytetrack|botsort] [--passes 5] [--out profiles/track_bench_mi355x.json]"""
 import argparse
 import json
 import statistics
@@ -31,7 +38,7 @@ sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 import yolosod_import  # noqa: E402,F401
 from bytetrack_ref import random_scene  # noqa: E402
-from yolosod_amd.engine.tracker import ByteTracker, ByteTrackerHost  # noqa: E402
+from yolosod_amd.engine import tracker as trackers  # noqa: E402
 
 B, FRAMES, OBJECTS, W, H, D, T = 32, 30, 100, 1920, 1080, 300, 256
 
@@ -40,20 +47,40 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--passes", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--tracker", choices=("bytetrack", "botsort"), default="bytetrack")
     a = ap.parse_args()
+    bot = a.tracker == "botsort"
     if not torch.cuda.is_available():
         raise SystemExit("bench_track: needs a GPU")
     dev = torch.device("cuda", 0)
-    scenes = [random_scene(seed=100 + s, objects=OBJECTS, frames=FRAMES, width=W, height=H, min_side=16, D=D)
-              for s in range(B)]
+    if bot:
+        from botsort_ref import IDENTITY, camera_scene
+        cams = [camera_scene(seed=100 + s, objects=OBJECTS, frames=FRAMES, width=W, height=H, min_side=16, D=D)
+                for s in range(B)]
+        scenes = [c[0] for c in cams]
+        warps = [torch.from_numpy(np.stack([IDENTITY if c[1][f] is None else c[1][f] for c in cams])).to(dev)
+                 for f in range(FRAMES)]
+        Dev, Host = trackers.BotSortTracker, trackers.BotSortTrackerHost
+    else:
+        scenes = [random_scene(seed=100 + s, objects=OBJECTS, frames=FRAMES, width=W, height=H, min_side=16, D=D)
+                  for s in range(B)]
+        warps = None
+        Dev, Host = trackers.ByteTracker, trackers.ByteTrackerHost
+
+    def step(t, f, host=False):
+        if not bot:
+            return t.update(outs[f].cpu(), counts[f].cpu()) if host else t.update(outs[f], counts[f])
+        if host:
+            return t.update(outs[f].cpu(), counts[f].cpu(), warps=warps[f].cpu())
+        return t.update(outs[f], counts[f], warps=warps[f])
     outs = [torch.from_numpy(np.stack([scenes[s][f][0] for s in range(B)])).to(dev) for f in range(FRAMES)]
     counts = [torch.tensor([scenes[s][f][1] for s in range(B)], dtype=torch.int32, device=dev) for f in range(FRAMES)]
     dets = float(np.mean([c.float().mean().item() for c in counts]))
 
-    trk = ByteTracker(streams=B, capacity=T, device=dev)
+    trk = Dev(streams=B, capacity=T, device=dev)
     dev_ids = []
     for f in range(FRAMES):  # warm-up pass; its results are the ones compared with the host's
-        tr = trk.update(outs[f], counts[f])
+        tr = step(trk, f)
         n = tr.counts.cpu().numpy()
         rows = tr.rows.cpu().numpy()
         dev_ids.append([rows[s, :n[s], 4].astype(int).tolist() for s in range(B)])
@@ -64,23 +91,24 @@ def main():
         ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(FRAMES)]
         for f in range(FRAMES):
             ev[f][0].record()
-            trk.update(outs[f], counts[f])
+            step(trk, f)
             ev[f][1].record()
         torch.cuda.synchronize()
         for f in range(FRAMES):
             per_frame[f].append(ev[f][0].elapsed_time(ev[f][1]))
     dev_ms = [statistics.median(v) for v in per_frame]
 
-    host = ByteTrackerHost(streams=B, capacity=T)
+    host = Host(streams=B, capacity=T)
     host_ms, same = [], True
     for f in range(FRAMES):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        tr = host.update(outs[f].cpu(), counts[f].cpu())
+        tr = step(host, f, host=True)
         host_ms.append((time.perf_counter() - t0) * 1e3)
         n = tr.counts.numpy()
         same &= [tr.rows[s, :n[s], 4].numpy().astype(int).tolist() for s in range(B)] == dev_ids[f]
-    r = dict(case="track_update", streams=B, frames=FRAMES, objects_per_stream=OBJECTS, frame=[W, H], capacity=T, rows=D,
+    r = dict(case="track_update", tracker=a.tracker, warps=bool(bot), streams=B, frames=FRAMES,
+             objects_per_stream=OBJECTS, frame=[W, H], capacity=T, rows=D,
              detections_per_frame=dets, live_tracks_last_frame=live, passes=a.passes,
              device_update_median_ms=statistics.median(dev_ms), device_update_worst_frame_ms=max(dev_ms),
              device_worst_frame=int(np.argmax(dev_ms)) + 1, host_update_median_ms=statistics.median(host_ms),

@@ -66,6 +66,7 @@ SIGNATURES = {
     "yolosod_track_workspace": (_sz, [_i, _i, _i]),
     "yolosod_track_reset": (_i, [_vp, _i, _i, _vp, _i, _vp]),
     "yolosod_track_update": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "yolosod_track_update_ex": (_i, [_vp, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "yolosod_debug_track_last": (_i, [_i]),
     "yolosod_tta_views": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "yolosod_tta_merge": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _f, _i, _f, _f, _vp]),
@@ -1908,13 +1909,21 @@ def track_reset(state, T, streams=None):
                    _stream(dev)), "track_reset")
 
 
-def track_update(state, T, out, counts, params, tracks=None, n_tracks=None, workspace=None):
+TRACK_MODELS = {"xyah": 0, "xywh": 1}  # the filter's model: ByteTrack, BoT-SORT (csrc/track.hip trk::XYAH / XYWH)
+
+
+def track_update(state, T, out, counts, params, tracks=None, n_tracks=None, workspace=None, model="xyah", warps=None):
     """One ByteTrack update of every stream, one launch and no host sync (yolosod_track_update; the reference's
-    ``BYTETracker.update`` per stream): ``state`` uint8 [B, track_state_bytes(T)] (reset once with
-    :func:`track_reset`), ``out`` fp32 [B, D, 6] and ``counts`` int32 [B] the padded NMS rows of each stream's next
-    frame, ``params`` a host sequence of 8 floats (``utils.bytetrack.params_vector``). Returns (tracks fp32 [B, T, 8] =
-    x1, y1, x2, y2, track_id, score, cls, idx, ascending track_id, zero padded; n_tracks int32 [B]) on ``out``'s device;
-    ``tracks`` / ``n_tracks`` / ``workspace`` may be passed in to be reused.
+    ``BYTETracker.update`` per stream). With ``model="xywh"`` it is BoT-SORT's update
+    (yolosod_track_update_ex): the XYWH filter and, if ``warps`` (fp64 [B, 2, 3] on the device, one
+    camera-motion matrix per stream) is given, the warp of every pool and unconfirmed track before the first
+    association; a stream whose warp has a non-finite entry skips it and counts it (``bad_warp``).
+
+    ``state`` uint8 [B, track_state_bytes(T)] (reset once with :func:`track_reset`), ``out`` fp32 [B, D, 6] and
+    ``counts`` int32 [B] the padded NMS rows of each stream's next frame, ``params`` a host sequence of 8 floats
+    (``utils.bytetrack.params_vector``). Returns (tracks fp32 [B, T, 8] = x1, y1, x2, y2, track_id, score, cls, idx,
+    ascending track_id, zero padded; n_tracks int32 [B]) on ``out``'s device; ``tracks`` / ``n_tracks`` /
+    ``workspace`` may be passed in to be reused.
 
     Everything the kernel relies on is checked here first: nothing is launched on arguments that fail."""
     import math
@@ -1922,7 +1931,14 @@ def track_update(state, T, out, counts, params, tracks=None, n_tracks=None, work
     import numpy as np
     lib = load_library()
     B = _track_state_check("track_update", state, T)
-    for t, name, dtype, dim in ((out, "out", torch.float32, 3), (counts, "counts", torch.int32, 1)):
+    if model not in TRACK_MODELS:
+        raise RuntimeError(f"track_update: model {model!r} unknown ({sorted(TRACK_MODELS)})")
+    if warps is not None and model != "xywh":
+        raise RuntimeError("track_update: warps with model 'xyah' (ByteTrack has no camera-motion step)")
+    checked = [(out, "out", torch.float32, 3), (counts, "counts", torch.int32, 1)]
+    if warps is not None:
+        checked.append((warps, "warps", torch.float64, 3))
+    for t, name, dtype, dim in checked:
         if not isinstance(t, torch.Tensor):
             raise TypeError(f"track_update: {name}: expected a tensor")
         if t.device.type != "cuda":
@@ -1942,6 +1958,8 @@ def track_update(state, T, out, counts, params, tracks=None, n_tracks=None, work
                            f"{B} streams)")
     if tuple(counts.shape) != (B,):
         raise RuntimeError(f"track_update: counts {tuple(counts.shape)} does not match {B} streams ([{B}] expected)")
+    if warps is not None and tuple(warps.shape) != (B, 2, 3):
+        raise RuntimeError(f"track_update: warps {tuple(warps.shape)} does not match {B} streams ([{B}, 2, 3] expected)")
     prm = np.ascontiguousarray(params, dtype=np.float32)
     if prm.shape != (8,) or not all(math.isfinite(float(v)) and float(v) >= 0.0 for v in prm):
         raise RuntimeError(f"track_update: params {prm!r} (8 finite values >= 0 expected)")
@@ -1962,24 +1980,38 @@ def track_update(state, T, out, counts, params, tracks=None, n_tracks=None, work
                                + (f" {list(shape)}" if shape else "") + f" on {dev}")
     if workspace.numel() < need:
         raise RuntimeError(f"track_update: workspace of {workspace.numel()} bytes, {need} needed")
-    _check(_launch(("track_update", (B, T, D), 0), dev, lib.yolosod_track_update, state.data_ptr(), B, T,
-                   out.data_ptr(), counts.data_ptr(), D, prm.ctypes.data, tracks.data_ptr(), n_tracks.data_ptr(),
-                   workspace.data_ptr(), workspace.numel(), _stream(dev)), "track_update")
+    if model == "xyah":
+        _check(_launch(("track_update", (B, T, D), 0), dev, lib.yolosod_track_update, state.data_ptr(), B, T,
+                       out.data_ptr(), counts.data_ptr(), D, prm.ctypes.data, tracks.data_ptr(), n_tracks.data_ptr(),
+                       workspace.data_ptr(), workspace.numel(), _stream(dev)), "track_update")
+    else:
+        _check(_launch(("track_update", (B, T, D), 1 + (warps is not None)), dev, lib.yolosod_track_update_ex,
+                       state.data_ptr(), B, T, out.data_ptr(), counts.data_ptr(), D, prm.ctypes.data,
+                       TRACK_MODELS[model], None if warps is None else warps.data_ptr(), tracks.data_ptr(),
+                       n_tracks.data_ptr(), workspace.data_ptr(), workspace.numel(), _stream(dev)), "track_update")
     return tracks, n_tracks
 
 
 def track_last_launch() -> dict:
     """Host-side facts of the last :func:`track_update` launch of this thread (yolosod_debug_track_last): T, D, B, the
     workspace layout (1: boxes and the [T, D] fp32 cost matrix per stream), lanes per workgroup, workspace bytes per
-    stream; all 0 before the first launch."""
+    stream; all 0 before the first launch. ``model`` (0 XYAH, 1 XYWH) and ``warps`` (0 / 1: whether warps were given)
+    of that launch are :func:`track_last_model`'s: this dict keeps its six keys."""
     lib = load_library()
     return {k: int(lib.yolosod_debug_track_last(i))
             for i, k in enumerate(("T", "D", "B", "layout", "lanes", "workspace_per_stream"))}
 
 
+def track_last_model() -> dict:
+    """``model`` (0 XYAH, 1 XYWH) and ``warps`` (0 / 1) of this thread's last track_update launch
+    (yolosod_debug_track_last indices 6 and 7)."""
+    lib = load_library()
+    return dict(model=int(lib.yolosod_debug_track_last(6)), warps=int(lib.yolosod_debug_track_last(7)))
+
+
 def track_state_fetch(state, T) -> list:
     """Debug fetch (a host sync): the tracker state parsed per stream into numpy arrays - ``frame``, ``next_id``,
-    ``overflow`` and per slot ``state`` (0 free, 1 Tracked, 2 Lost, 3 Removed but listed as lost), ``flags`` (1
+    ``overflow``, ``bad_warp`` and per slot ``state`` (0 free, 1 Tracked, 2 Lost, 3 Removed but listed as lost), ``flags`` (1
     activated, 2 the id was removed once), ``tid``, ``start``, ``last``, ``idx``, ``score``, ``cls``, ``mean`` [T, 8]
     and ``cov`` [T, 8, 8] (fp64) - plus ``raw``, the stream's bytes."""
     import numpy as np
@@ -1994,7 +2026,8 @@ def track_state_fetch(state, T) -> list:
         o += 64 * T
         cov = r[o:o + 512 * T].view(np.float64).reshape(8, 8, T).transpose(2, 0, 1).copy()
         o += 512 * T
-        d = dict(frame=int(hdr[0]), next_id=int(hdr[1]), overflow=int(hdr[2]), mean=mean, cov=cov, raw=r)
+        d = dict(frame=int(hdr[0]), next_id=int(hdr[1]), overflow=int(hdr[2]), bad_warp=int(hdr[3]), mean=mean, cov=cov,
+                 raw=r)
         for name, dt in (("state", np.int32), ("flags", np.int32), ("tid", np.int32), ("start", np.int32),
                          ("last", np.int32), ("idx", np.int32), ("score", np.float32), ("cls", np.float32)):
             d[name] = r[o:o + 4 * T].view(dt).copy()

@@ -32,6 +32,15 @@
 // column per row. A private column can only end a path: it is free whenever its row is in the tree, its dual stays 0,
 // so only the cheapest one reached so far is kept, in registers. The column scan and the argmin run across the lanes.
 // Every loop has a static bound from T and D, stated at the loop; none depends on floating-point convergence.
+//
+// BoT-SORT (the definition is yolo-sod_amd/utils/botsort.py) is the second instantiation of the same
+// kernel, MODEL 1: the XYWH filter (kalman_filter.py:289-491: noise from the width and the height separately, state
+// (cx, cy, w, h) and its velocities), both size velocities zeroed for tracks that are not Tracked (bot_sort.py:126-129),
+// track boxes from (cx, cy, w, h) (bot_sort.py:110-117), and one more phase between predict and the first association:
+//   gmc         every pool and unconfirmed track warped by the stream's 2x3 camera-motion matrix (STrack.multi_gmc,
+//               byte_tracker.py:103-120), one lane per track, fp64, as the 2x2 blocks of kron(I4, R); a warp with a
+//               non-finite entry is skipped and counted in the header (bad_warp)
+// MODEL 0 is ByteTrack as before: it has no gmc phase and never touches the fourth header word.
 #include "common.h"
 
 namespace ys {
@@ -44,7 +53,8 @@ constexpr int ST_FREE = 0, ST_TRACKED = 1, ST_LOST = 2, ST_REMOVED = 3;
 constexpr int FL_ACT = 1, FL_WASREM = 2;
 constexpr int TI_POOL = 1, TI_OLDLOST = 2, TI_MATCHED = 4, TI_NEWLOST = 8, TI_UNCONF = 16;
 constexpr int HDR_BYTES = 64;
-constexpr int HDR_FRAME = 0, HDR_NEXT_ID = 1, HDR_OVERFLOW = 2;
+constexpr int HDR_FRAME = 0, HDR_NEXT_ID = 1, HDR_OVERFLOW = 2, HDR_BAD_WARP = 3;
+constexpr int XYAH = 0, XYWH = 1;  // the filter's model: ByteTrack, BoT-SORT
 constexpr double STD_POS = 1.0 / 20, STD_VEL = 1.0 / 160;  // kalman_filter.py:62-63
 
 __host__ __device__ inline size_t state_bytes(int T) { return HDR_BYTES + (size_t)T * (72 * 8 + 8 * 4); }
@@ -146,10 +156,19 @@ __device__ __forceinline__ bool det_geom(const float* r, float4& xyxy, float4& x
   xyah = make_float4(left + w / 2.f, top + h / 2.f, w / (valid ? h : 1.f), h);
   return valid;
 }
-// a track's xyxy from its fp64 mean, one cast: bytetrack.track_boxes
+// the filter's measurement of a detection row: xyah, or for XYWH (l + w / 2, t + h / 2, w, h) (bot_sort.py:140-144)
+template <int MODEL>
+__device__ __forceinline__ float4 det_meas(const float* r) {
+  float4 xyxy, z;
+  det_geom(r, xyxy, z);
+  if (MODEL == XYWH) z.z = r[2] - r[0];
+  return z;
+}
+// a track's xyxy from its fp64 mean, one cast: bytetrack.track_boxes / botsort.track_boxes_xywh
+template <int MODEL>
 __device__ __forceinline__ float4 track_box(const View& st, int T, int slot) {
   const double m0 = st.mean[slot], m1 = st.mean[T + slot], m2 = st.mean[2 * T + slot], m3 = st.mean[3 * T + slot];
-  const double w = m2 * m3, left = m0 - w / 2.0, top = m1 - m3 / 2.0;
+  const double w = MODEL == XYWH ? m2 : m2 * m3, left = m0 - w / 2.0, top = m1 - m3 / 2.0;
   return make_float4((float)left, (float)top, (float)(w + left), (float)(m3 + top));
 }
 // 1 - IoU of track box a against box b: bytetrack.iou_cost
@@ -162,20 +181,32 @@ __device__ __forceinline__ float iou_cost(float4 a, float4 b) {
   return 1.f - inter / (area + 1e-7f);
 }
 
-// ---- Kalman filter, XYAH, fp64, one lane per track -----------------------------------------------------------------
+// ---- Kalman filter, XYAH or XYWH, fp64, one lane per track ---------------------------------------------------------
+template <int MODEL>
 __device__ void kf_initiate(const View& st, int T, int slot, float4 z) {
-  const double p = (double)(0.1f * z.w), v = (double)(0.0625f * z.w);  // fp32 products, then promoted
-  const double std[8] = {p, p, 1e-2, p, v, v, 1e-5, v};
+  double var[8];
+  if (MODEL == XYWH) {  // kalman_filter.py:351-361: eight fp32 products, squared in fp32 (the list is all np.float32)
+    const float pw = 0.1f * z.z, ph = 0.1f * z.w, vw = 0.0625f * z.z, vh = 0.0625f * z.w;
+    const float v32[8] = {pw * pw, ph * ph, pw * pw, ph * ph, vw * vw, vh * vh, vw * vw, vh * vh};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) var[i] = (double)v32[i];
+  } else {
+    const double p = (double)(0.1f * z.w), v = (double)(0.0625f * z.w);  // fp32 products, then promoted
+    const double std[8] = {p, p, 1e-2, p, v, v, 1e-5, v};
+#pragma unroll
+    for (int i = 0; i < 8; ++i) var[i] = std[i] * std[i];
+  }
   const double m[4] = {(double)z.x, (double)z.y, (double)z.z, (double)z.w};
 #pragma unroll
   for (int i = 0; i < 8; ++i) st.mean[i * T + slot] = i < 4 ? m[i] : 0.0;
 #pragma unroll
   for (int i = 0; i < 8; ++i)
 #pragma unroll
-    for (int j = 0; j < 8; ++j) st.cov[(i * 8 + j) * T + slot] = i == j ? std[i] * std[i] : 0.0;
+    for (int j = 0; j < 8; ++j) st.cov[(i * 8 + j) * T + slot] = i == j ? var[i] : 0.0;
 }
 
 // mean' = F mean, P' = F P F' + Q with F = [[I, I], [0, I]]: rows, then columns, then the diagonal; no 8x8 products
+template <int MODEL>
 __device__ void kf_predict(const View& st, int T, int slot, bool zero_vh) {
   double m[8], P[64];
 #pragma unroll
@@ -183,8 +214,17 @@ __device__ void kf_predict(const View& st, int T, int slot, bool zero_vh) {
 #pragma unroll
   for (int i = 0; i < 64; ++i) P[i] = st.cov[i * T + slot];
   if (zero_vh) m[7] = 0.0;
-  const double sp = STD_POS * m[3], sv = STD_VEL * m[3];
-  const double q[8] = {sp * sp, sp * sp, 1e-2 * 1e-2, sp * sp, sv * sv, sv * sv, 1e-5 * 1e-5, sv * sv};
+  if (MODEL == XYWH && zero_vh) m[6] = 0.0;  // bot_sort.py:126-129
+  double q[8];
+  if (MODEL == XYWH) {  // kalman_filter.py:448-460
+    const double pw = STD_POS * m[2], ph = STD_POS * m[3], vw = STD_VEL * m[2], vh = STD_VEL * m[3];
+    q[0] = pw * pw, q[1] = ph * ph, q[2] = pw * pw, q[3] = ph * ph;
+    q[4] = vw * vw, q[5] = vh * vh, q[6] = vw * vw, q[7] = vh * vh;
+  } else {
+    const double sp = STD_POS * m[3], sv = STD_VEL * m[3];
+    q[0] = sp * sp, q[1] = sp * sp, q[2] = 1e-2 * 1e-2, q[3] = sp * sp;
+    q[4] = sv * sv, q[5] = sv * sv, q[6] = 1e-5 * 1e-5, q[7] = sv * sv;
+  }
 #pragma unroll
   for (int i = 0; i < 4; ++i) m[i] = m[i] + m[i + 4];
 #pragma unroll
@@ -204,14 +244,15 @@ __device__ void kf_predict(const View& st, int T, int slot, bool zero_vh) {
 }
 
 // project, 4x4 Cholesky solve (unrolled, lower triangle as scipy's cho_factor(lower=True)), mean and covariance update
+template <int MODEL>
 __device__ void kf_update(const View& st, int T, int slot, float4 z32) {
   double m[8], P[64];
 #pragma unroll
   for (int i = 0; i < 8; ++i) m[i] = st.mean[i * T + slot];
 #pragma unroll
   for (int i = 0; i < 64; ++i) P[i] = st.cov[i * T + slot];
-  const double sp = STD_POS * m[3];
-  const double r[4] = {sp * sp, sp * sp, 1e-1 * 1e-1, sp * sp};
+  const double sp = STD_POS * m[3], spw = STD_POS * m[2];
+  const double r[4] = {MODEL == XYWH ? spw * spw : sp * sp, sp * sp, MODEL == XYWH ? spw * spw : 1e-1 * 1e-1, sp * sp};
   double S[16];
 #pragma unroll
   for (int i = 0; i < 4; ++i)
@@ -255,17 +296,46 @@ __device__ void kf_update(const View& st, int T, int slot, float4 z32) {
   }
 }
 
+// ---- camera motion (STrack.multi_gmc, byte_tracker.py:103-120), fp64, one lane per track ----------------------------
+// mean' = kron(I4, R) mean with the translation added to (cx, cy); P' = kron(I4, R) P kron(I4, R)': the sixteen 2x2
+// blocks R C_ij R', each read, transformed and written in place. R = [[a, b], [c, d]], t = (tx, ty).
+__device__ void gmc_apply(const View& st, int T, int slot, double a, double b, double tx, double c, double d,
+                          double ty) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const double x = st.mean[(2 * i) * T + slot], y = st.mean[(2 * i + 1) * T + slot];
+    double nx = a * x + b * y, ny = c * x + d * y;
+    if (i == 0) nx += tx, ny += ty;
+    st.mean[(2 * i) * T + slot] = nx;
+    st.mean[(2 * i + 1) * T + slot] = ny;
+  }
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      double* p = st.cov + ((size_t)(2 * i) * 8 + 2 * j) * T + slot;  // C_ij = [[p00, p01], [p10, p11]]
+      const double p00 = p[0], p01 = p[T], p10 = p[8 * (size_t)T], p11 = p[9 * (size_t)T];
+      const double m00 = a * p00 + b * p10, m01 = a * p01 + b * p11;  // R C_ij
+      const double m10 = c * p00 + d * p10, m11 = c * p01 + d * p11;
+      p[0] = m00 * a + m01 * b;  // (R C_ij) R'
+      p[T] = m00 * c + m01 * d;
+      p[8 * (size_t)T] = m10 * a + m11 * b;
+      p[9 * (size_t)T] = m10 * c + m11 * d;
+    }
+}
+
 // ---- one association --------------------------------------------------------------------------------------------------
 // s.rows[0..n_r) slots and s.cols[0..n_c) detection rows, both ascending. Fills the cost matrix, solves the exact
 // assignment, applies the matches (Kalman update, state) and gives every unmatched slot the state ``unmatched`` (-1:
 // leave it). Called by every lane.
+template <int MODEL>
 __device__ void associate(Sh& s, const View& st, int T, int n_r, int n_c, float thresh, bool fused, float* cost,
                           float4* tbox, const float4* dbox, const float* det, int frame, int unmatched) {
   const int tid = threadIdx.x;
   for (int r = tid; r < n_r; r += NT) {  // <= T / NT passes
     s.x[r] = -1;
     s.u[r] = 0.0;
-    if (n_c > 0) tbox[r] = track_box(st, T, s.rows[r]);
+    if (n_c > 0) tbox[r] = track_box<MODEL>(st, T, s.rows[r]);
   }
   for (int c = tid; c < n_c; c += NT) {  // <= D / NT passes
     s.v[c] = 0.0;
@@ -386,9 +456,8 @@ __device__ void associate(Sh& s, const View& st, int T, int n_r, int n_c, float 
     if (c >= 0) {
       const int d = s.cols[c];
       const float* row = det + (size_t)d * 6;
-      float4 xyxy, xyah;
-      det_geom(row, xyxy, xyah);
-      kf_update(st, T, slot, xyah);  // STrack.update / re_activate(new_id=False), byte_tracker.py:137-178
+      // STrack.update / re_activate(new_id=False), byte_tracker.py:137-178
+      kf_update<MODEL>(st, T, slot, det_meas<MODEL>(row));
       st.state[slot] = ST_TRACKED;
       st.flags[slot] |= FL_ACT;
       st.last[slot] = frame;
@@ -405,10 +474,11 @@ __device__ void associate(Sh& s, const View& st, int T, int n_r, int n_c, float 
   __syncthreads();
 }
 
+template <int MODEL>
 __global__ __launch_bounds__(NT) void track_update_kernel(char* __restrict__ state, int T, const float* __restrict__ det_all,
                                                           const int* __restrict__ counts, int D, Params prm,
                                                           float* __restrict__ tracks, int* __restrict__ n_tracks,
-                                                          char* __restrict__ workspace) {
+                                                          char* __restrict__ workspace, const double* __restrict__ warps) {
   __shared__ Sh s;
   const int b = blockIdx.x, tid = threadIdx.x;
   const View st = view(state + (size_t)b * state_bytes(T), T);
@@ -419,7 +489,7 @@ __global__ __launch_bounds__(NT) void track_update_kernel(char* __restrict__ sta
   const float* det = det_all + (size_t)b * D * 6;
   const int n = min(max(counts[b], 0), D);
   const int frame = st.hdr[HDR_FRAME] + 1;  // byte_tracker.py:295
-  const int next_id0 = st.hdr[HDR_NEXT_ID], overflow0 = st.hdr[HDR_OVERFLOW];
+  const int next_id0 = st.hdr[HDR_NEXT_ID], overflow0 = st.hdr[HDR_OVERFLOW], bad_warp0 = st.hdr[HDR_BAD_WARP];
 
   // detections (byte_tracker.py:301-317)
   for (int d = tid; d < n; d += NT) {  // <= D / NT passes
@@ -438,28 +508,42 @@ __global__ __launch_bounds__(NT) void track_update_kernel(char* __restrict__ sta
     int ti = 0;
     if ((sv == ST_TRACKED && act) || sv == ST_LOST || sv == ST_REMOVED) {
       ti = TI_POOL | (sv != ST_TRACKED ? TI_OLDLOST : 0);
-      kf_predict(st, T, t, sv != ST_TRACKED);
+      kf_predict<MODEL>(st, T, t, sv != ST_TRACKED);
     } else if (sv == ST_TRACKED) {
       ti = TI_UNCONF;
     }
     s.tinfo[t] = (unsigned char)ti;
+  }
+  // camera motion (byte_tracker.py:332-335): the pool after its prediction and the unconfirmed tracks, which were not
+  // predicted. The lane that owns slot t here owned it in the loop above, so no barrier lies between the two. The six
+  // values and the finite check are the same for every lane of the workgroup.
+  int bad_warp = 0;
+  if (MODEL == XYWH && warps) {
+    const double* h = warps + (size_t)b * 6;
+    const double a = h[0], bb = h[1], tx = h[2], c = h[3], d = h[4], ty = h[5];
+    if (isfinite(a) && isfinite(bb) && isfinite(tx) && isfinite(c) && isfinite(d) && isfinite(ty)) {
+      for (int t = tid; t < T; t += NT)  // T / NT passes
+        if (s.tinfo[t] & (TI_POOL | TI_UNCONF)) gmc_apply(st, T, t, a, bb, tx, c, d, ty);
+    } else {
+      bad_warp = 1;
+    }
   }
   __syncthreads();
 
   // first association (byte_tracker.py:337-348)
   int n_r = compact(T, s.rows, s.scan, [&](int t) { return (s.tinfo[t] & TI_POOL) != 0; });
   int n_c = compact(n, s.cols, s.scan, [&](int d) { return s.tier[d] == 1; });
-  associate(s, st, T, n_r, n_c, prm.match, prm.fuse != 0, cost, tbox, dbox, det, frame, -1);
+  associate<MODEL>(s, st, T, n_r, n_c, prm.match, prm.fuse != 0, cost, tbox, dbox, det, frame, -1);
   // second association (byte_tracker.py:350-369)
   n_r = compact(T, s.rows, s.scan, [&](int t) {
     return (s.tinfo[t] & (TI_POOL | TI_MATCHED)) == TI_POOL && st.state[t] == ST_TRACKED;
   });
   n_c = compact(n, s.cols, s.scan, [&](int d) { return s.tier[d] == 2; });
-  associate(s, st, T, n_r, n_c, prm.second, false, cost, tbox, dbox, det, frame, ST_LOST);
+  associate<MODEL>(s, st, T, n_r, n_c, prm.second, false, cost, tbox, dbox, det, frame, ST_LOST);
   // unconfirmed tracks (byte_tracker.py:371-380)
   n_r = compact(T, s.rows, s.scan, [&](int t) { return (s.tinfo[t] & TI_UNCONF) != 0; });
   n_c = compact(n, s.cols, s.scan, [&](int d) { return s.tier[d] == 1 && s.dmatch[d] < 0; });
-  associate(s, st, T, n_r, n_c, prm.unconf, prm.fuse != 0, cost, tbox, dbox, det, frame, ST_FREE);
+  associate<MODEL>(s, st, T, n_r, n_c, prm.unconf, prm.fuse != 0, cost, tbox, dbox, det, frame, ST_FREE);
 
   // births (byte_tracker.py:382-387): ascending row index into the lowest free slots
   const int n_free = compact(T, s.rows, s.scan, [&](int t) { return st.state[t] == ST_FREE; });
@@ -470,9 +554,7 @@ __global__ __launch_bounds__(NT) void track_update_kernel(char* __restrict__ sta
   for (int k = tid; k < n_born; k += NT) {  // <= T / NT passes
     const int slot = s.rows[k], d = s.cols[k];
     const float* row = det + (size_t)d * 6;
-    float4 xyxy, xyah;
-    det_geom(row, xyxy, xyah);
-    kf_initiate(st, T, slot, xyah);
+    kf_initiate<MODEL>(st, T, slot, det_meas<MODEL>(row));
     st.state[slot] = ST_TRACKED;
     st.flags[slot] = frame == 1 ? FL_ACT : 0;  // byte_tracker.py:130-131
     st.tid[slot] = next_id0 + k;
@@ -506,7 +588,7 @@ __global__ __launch_bounds__(NT) void track_update_kernel(char* __restrict__ sta
   const int n_b = compact(T, s.cols, s.scan, [&](int t) { return st.state[t] == ST_LOST || st.state[t] == ST_REMOVED; });
   if (n_a > 0 && n_b > 0) {
     for (int t = tid; t < T; t += NT)  // T / NT passes
-      if (st.state[t] != ST_FREE) tbox[t] = track_box(st, T, t);
+      if (st.state[t] != ST_FREE) tbox[t] = track_box<MODEL>(st, T, t);
     __syncthreads();
     for (int e = tid; e < n_a * n_b; e += NT) {  // <= T * T / (4 NT) passes
       const int ia = e / n_b, ib = e - ia * n_b;
@@ -532,7 +614,7 @@ __global__ __launch_bounds__(NT) void track_update_kernel(char* __restrict__ sta
       const int slot = s.rows[k], id = s.cols[k];
       int rank = 0;
       for (int q = 0; q < n_live; ++q) rank += s.cols[q] < id ? 1 : 0;  // <= T steps; ids are distinct
-      const float4 box = track_box(st, T, slot);
+      const float4 box = track_box<MODEL>(st, T, slot);
       float* o = out + (size_t)rank * 8;
       o[0] = box.x, o[1] = box.y, o[2] = box.z, o[3] = box.w;
       o[4] = (float)id, o[5] = st.score[slot], o[6] = st.cls[slot], o[7] = (float)st.idx[slot];
@@ -547,6 +629,7 @@ __global__ __launch_bounds__(NT) void track_update_kernel(char* __restrict__ sta
     st.hdr[HDR_FRAME] = frame;
     st.hdr[HDR_NEXT_ID] = next_id0 + n_born;
     st.hdr[HDR_OVERFLOW] = overflow0 + (n_want - n_born);
+    if (MODEL == XYWH && bad_warp) st.hdr[HDR_BAD_WARP] = bad_warp0 + 1;
   }
 }
 
@@ -560,7 +643,7 @@ __global__ __launch_bounds__(NT) void track_reset_kernel(char* __restrict__ stat
   for (int i = threadIdx.x; i < words; i += NT) w[i] = i == HDR_NEXT_ID ? 1 : 0;  // words / NT passes
 }
 
-static thread_local int g_last[6] = {0, 0, 0, 0, 0, 0};
+static thread_local int g_last[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 
 static int check_shape(const char* what, int B, int T) {
   YS_CHECK_ARG(B >= 1, "%s: B=%d", what, B);
@@ -593,33 +676,60 @@ YS_EXPORT int yolosod_track_reset(void* state, int B, int T, const int* streams,
   return 0;
 }
 
-YS_EXPORT int yolosod_track_update(void* state, int B, int T, const float* det, const int* counts, int D,
-                                   const float* params, float* tracks, int* n_tracks, void* workspace, size_t ws_bytes,
-                                   void* stream) {
-  using namespace trk;
-  YS_CHECK_ARG(state && det && counts && params && tracks && n_tracks && workspace, "track_update: null pointer");
-  if (check_shape("track_update", B, T)) return -1;
-  YS_CHECK_ARG(D >= 1 && D <= MAXN, "track_update: D=%d unsupported (1..%d)", D, MAXN);
-  YS_CHECK_ARG(ws_bytes >= (size_t)B * ws_stream_bytes(T, D), "track_update: workspace of %zu bytes, %zu needed", ws_bytes,
+namespace ys {
+namespace trk {
+// the checks and the launch of both entry points; ``what`` names the caller in the messages
+static int launch_update(const char* what, void* state, int B, int T, const float* det, const int* counts, int D,
+                         const float* params, int model, const double* warps, float* tracks, int* n_tracks,
+                         void* workspace, size_t ws_bytes, void* stream) {
+  YS_CHECK_ARG(state && det && counts && params && tracks && n_tracks && workspace, "%s: null pointer", what);
+  if (check_shape(what, B, T)) return -1;
+  YS_CHECK_ARG(D >= 1 && D <= MAXN, "%s: D=%d unsupported (1..%d)", what, D, MAXN);
+  YS_CHECK_ARG(model == XYAH || model == XYWH, "%s: model=%d unknown (0 XYAH, 1 XYWH)", what, model);
+  YS_CHECK_ARG(!(warps && model == XYAH), "%s: warps with model 0 (XYAH, ByteTrack has no camera-motion step)", what);
+  YS_CHECK_ARG(ws_bytes >= (size_t)B * ws_stream_bytes(T, D), "%s: workspace of %zu bytes, %zu needed", what, ws_bytes,
                (size_t)B * ws_stream_bytes(T, D));
   YS_CHECK_ARG(((uintptr_t)state & 7) == 0 && ((uintptr_t)workspace & 15) == 0 && ((uintptr_t)det & 3) == 0 &&
                    ((uintptr_t)counts & 3) == 0 && ((uintptr_t)tracks & 3) == 0 && ((uintptr_t)n_tracks & 3) == 0,
-               "track_update: misaligned pointer");
+               "%s: misaligned pointer", what);
+  YS_CHECK_ARG(((uintptr_t)warps & 7) == 0, "%s: misaligned warps (8-byte alignment expected)", what);
   for (int i = 0; i < 8; ++i)
-    YS_CHECK_ARG(params[i] >= 0.f && params[i] <= 3.402823466e+38f, "track_update: params[%d] is %g (finite and >= 0 expected)",
+    YS_CHECK_ARG(params[i] >= 0.f && params[i] <= 3.402823466e+38f, "%s: params[%d] is %g (finite and >= 0 expected)", what,
                  i, (double)params[i]);
   Params prm;
   prm.high = params[0], prm.low = params[1], prm.newt = params[2], prm.match = params[3], prm.second = params[4];
   prm.unconf = params[5];
   prm.max_time_lost = params[6] > 2147483000.f ? 2147483000 : (int)params[6];
   prm.fuse = params[7] != 0.f;
-  hipLaunchKernelGGL(track_update_kernel, dim3((unsigned)B), dim3(NT), 0, (hipStream_t)stream, (char*)state, T, det,
-                     counts, D, prm, tracks, n_tracks, (char*)workspace);
-  YS_CHECK_LAUNCH("track_update");
+  if (model == XYWH)
+    hipLaunchKernelGGL(track_update_kernel<XYWH>, dim3((unsigned)B), dim3(NT), 0, (hipStream_t)stream, (char*)state, T,
+                       det, counts, D, prm, tracks, n_tracks, (char*)workspace, warps);
+  else
+    hipLaunchKernelGGL(track_update_kernel<XYAH>, dim3((unsigned)B), dim3(NT), 0, (hipStream_t)stream, (char*)state, T,
+                       det, counts, D, prm, tracks, n_tracks, (char*)workspace, (const double*)nullptr);
+  YS_CHECK_LAUNCH(what);
   g_last[0] = T, g_last[1] = D, g_last[2] = B, g_last[3] = 1, g_last[4] = NT, g_last[5] = (int)ws_stream_bytes(T, D);
+  g_last[6] = model, g_last[7] = warps ? 1 : 0;
   return 0;
+}
+}  // namespace trk
+}  // namespace ys
+
+YS_EXPORT int yolosod_track_update(void* state, int B, int T, const float* det, const int* counts, int D,
+                                   const float* params, float* tracks, int* n_tracks, void* workspace, size_t ws_bytes,
+                                   void* stream) {
+  return trk::launch_update("track_update", state, B, T, det, counts, D, params, trk::XYAH, nullptr, tracks, n_tracks,
+                            workspace, ws_bytes, stream);
+}
+
+YS_EXPORT int yolosod_track_update_ex(void* state, int B, int T, const float* det, const int* counts, int D,
+                                      const float* params, int model, const double* warps, float* tracks, int* n_tracks,
+                                      void* workspace, size_t ws_bytes, void* stream) {
+  return trk::launch_update("track_update_ex", state, B, T, det, counts, D, params, model, warps, tracks, n_tracks,
+                            workspace, ws_bytes, stream);
 }
 
 // host-side facts of this thread's last track_update launch: 0 T, 1 D, 2 B, 3 the workspace layout (1: per stream
-// track boxes [T], detection boxes [D], cost matrix [T x D] fp32), 4 lanes per workgroup, 5 workspace bytes per stream
-YS_EXPORT int yolosod_debug_track_last(int what) { return (what >= 0 && what < 6) ? trk::g_last[what] : -1; }
+// track boxes [T], detection boxes [D], cost matrix [T x D] fp32), 4 lanes per workgroup, 5 workspace bytes per stream,
+// 6 the model (0 XYAH, 1 XYWH), 7 whether warps were given
+YS_EXPORT int yolosod_debug_track_last(int what) { return (what >= 0 && what < 8) ? trk::g_last[what] : -1; }

@@ -235,22 +235,23 @@ class DetectionPredictor:
         return out, counts, index, ing.shapes
 
     @torch.inference_mode()
-    def track_padded(self, frames):
+    def track_padded(self, frames, warps=None):
         """:meth:`predict_padded`, then the tracker's update on the rows (after ``scale_boxes_padded``: tracks live in
         each stream's own pixels): (rows [B, T, 8], n_tracks [B], out, counts, index), no host sync. ``frames[i]`` is
         the next frame of stream ``i``; the batch must be the tracker's ``streams``. The second-tier association only
         sees detections the NMS lets through: it needs ``conf <= track_low_thresh`` (the reference's track mode has
-        the same trait; the default ``conf`` stays 0.25)."""
-        _require_tracker(self.tracker, len(frames), "DetectionPredictor")
+        the same trait; the default ``conf`` stays 0.25). ``warps`` [B, 2, 3], for a BoT-SORT tracker: every stream's
+        camera motion since its previous frame, in that stream's own frame pixels (not the letterboxed ones)."""
+        _require_tracker(self.tracker, len(frames), "DetectionPredictor", warps)
         out, counts, index = self.predict_padded(frames)
-        rows, n_tracks = self.tracker.update(out, counts)
+        rows, n_tracks = _tracker_update(self.tracker, out, counts, warps)
         return rows, n_tracks, out, counts, index
 
-    def track(self, frames):
+    def track(self, frames, warps=None):
         """Per stream :class:`~.tracker.Tracked` (boxes [n, 7] = xyxy, id, conf, cls; index; orig_shape); syncs for
         the per-stream lists."""
         from .tracker import tracked_lists
-        rows, n_tracks, out, counts, index = self.track_padded(frames)
+        rows, n_tracks, out, counts, index = self.track_padded(frames, warps)
         if isinstance(frames, (list, tuple)):
             shapes = [tuple(int(v) for v in f.shape[:2]) for f in frames]
         else:
@@ -489,19 +490,19 @@ class SlicedPredictor:
         kernels (the frames are not uploaded again)."""
         return self._predict_guarded(frames)[0]
 
-    def track_padded(self, frames):
+    def track_padded(self, frames, warps=None):
         """:meth:`predict_padded`, then the tracker's update on the rows in frame pixels: (rows [F, T, 8], n_tracks [F],
         out, counts, index), no host sync; as ``DetectionPredictor.track_padded`` (``conf <= track_low_thresh`` for a
-        second tier)."""
-        _require_tracker(self.tracker, len(frames), "SlicedPredictor")
+        second tier; ``warps`` [F, 2, 3] in frame pixels for a BoT-SORT tracker)."""
+        _require_tracker(self.tracker, len(frames), "SlicedPredictor", warps)
         out, counts, index = self.predict_padded(frames)
-        rows, n_tracks = self.tracker.update(out, counts)
+        rows, n_tracks = _tracker_update(self.tracker, out, counts, warps)
         return rows, n_tracks, out, counts, index
 
-    def track(self, frames):
+    def track(self, frames, warps=None):
         """Per stream :class:`~.tracker.Tracked`; ``index`` is ``slot * A + anchor`` (:meth:`locate`)."""
         from .tracker import tracked_lists
-        rows, n_tracks, out, counts, index = self.track_padded(frames)
+        rows, n_tracks, out, counts, index = self.track_padded(frames, warps)
         return tracked_lists(rows, n_tracks, index, [tuple(int(v) for v in f.shape[:2]) for f in frames])
 
     def __call__(self, frames):
@@ -510,11 +511,20 @@ class SlicedPredictor:
         return [Detections(out[i, : n[i]], index[i, : n[i]], plan.shapes[i]) for i in range(len(n))]
 
 
-def _require_tracker(tracker, batch, who):
+def _require_tracker(tracker, batch, who, warps=None):
     if tracker is None:
         raise RuntimeError(f"{who}.track: constructed without a tracker (tracker=ByteTracker(streams=...))")
     if int(batch) != tracker.streams:
         raise ValueError(f"{who}.track: batch of {int(batch)} frames for a tracker of {tracker.streams} streams")
+    if warps is not None:
+        from .tracker import takes_warps
+        if not takes_warps(tracker):
+            raise ValueError(f"{who}.track: warps given, but the tracker is a {type(tracker).__name__}: ByteTrack has "
+                             "no camera-motion step (tracker=BotSortTracker(streams=...))")
+
+
+def _tracker_update(tracker, out, counts, warps):
+    return tracker.update(out, counts) if warps is None else tracker.update(out, counts, warps)
 
 
 def shard_bounds(n: int, rank: int, world: int):

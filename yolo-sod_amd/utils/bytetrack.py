@@ -227,6 +227,22 @@ class StreamTracker:
     def _expired_drop_now(self):
         return False  # byte_tracker.py:399 subtracts the removed list from before this frame (Q4)
 
+    # the pieces another motion model replaces (utils/botsort.py): the filter, the boxes, the step before association
+    _kf_initiate = staticmethod(kf_initiate)
+    _kf_predict = staticmethod(kf_predict)
+    _kf_update = staticmethod(kf_update)
+    _track_boxes = staticmethod(track_boxes)
+    _ZEROED = (7,)  # the velocities zeroed before a track that is not Tracked is predicted (byte_tracker.py:96-97)
+
+    def _measurements(self, rows, xyah):
+        return xyah  # fp32 [n, 4], what the filter is initiated and updated with
+
+    def _motion(self, pool, unconfirmed):
+        for i in self._predicted(pool, unconfirmed):  # byte_tracker.py:331
+            if self._zero_vh(i):
+                self.mean[i, list(self._ZEROED)] = 0.0
+            self.mean[i], self.cov[i] = self._kf_predict(self.mean[i], self.cov[i])
+
     # ------------------------------------------------------------------------------------------------------------------
     def _tell(self, kind, **facts):
         if self.observer is not None:
@@ -239,7 +255,7 @@ class StreamTracker:
         dets = list(dets)
         if not slots or not dets:
             return [], slots, dets
-        cost = iou_cost(track_boxes(self.mean[slots]), dxyxy[dets], dscore[dets] if fused else None)
+        cost = iou_cost(self._track_boxes(self.mean[slots]), dxyxy[dets], dscore[dets] if fused else None)
         m = self._assign(cost, thresh)
         self._tell("assign", which=which, cost=cost, thresh=thresh, matches=m, slots=slots, dets=dets)
         ms = {i for i, _ in m}
@@ -249,7 +265,7 @@ class StreamTracker:
 
     def _matched(self, slot, row, xyah, rows, f):
         """STrack.update / re_activate(new_id=False) (byte_tracker.py:137-149, 165-178): the same in slot terms."""
-        self.mean[slot], self.cov[slot] = kf_update(self.mean[slot], self.cov[slot], xyah[row])
+        self.mean[slot], self.cov[slot] = self._kf_update(self.mean[slot], self.cov[slot], xyah[row])
         self.state[slot] = TRACKED
         self.activated[slot] = True
         self.last[slot] = f
@@ -264,6 +280,7 @@ class StreamTracker:
         self.frame += 1  # byte_tracker.py:295
         f = self.frame
         dxyxy, xyah, valid = det_boxes(rows)
+        xyah = self._measurements(rows, xyah)
         s = rows[:, 4]
         with np.errstate(invalid="ignore"):
             high = valid & (s >= self.high)                     # byte_tracker.py:307
@@ -276,10 +293,7 @@ class StreamTracker:
         unconfirmed = [int(i) for i in np.flatnonzero((st0 == TRACKED) & ~self.activated)]
         pool = [int(i) for i in np.flatnonzero(((st0 == TRACKED) & self.activated) | (st0 == LOST) | (st0 == REMOVED))]
         old_lost = [i for i in pool if st0[i] != TRACKED]
-        for i in self._predicted(pool, unconfirmed):  # byte_tracker.py:331
-            if self._zero_vh(i):
-                self.mean[i, 7] = 0.0
-            self.mean[i], self.cov[i] = kf_predict(self.mean[i], self.cov[i])
+        self._motion(pool, unconfirmed)
 
         # first association (byte_tracker.py:337-348)
         m1, u_track, u_det = self._associate(1, pool, d_high, dxyxy, s, self.match_thresh, self.fuse)
@@ -309,7 +323,7 @@ class StreamTracker:
                 self.overflow += 1
                 continue
             slot = int(free[0])
-            self.mean[slot], self.cov[slot] = kf_initiate(xyah[row])
+            self.mean[slot], self.cov[slot] = self._kf_initiate(xyah[row])
             self.state[slot] = TRACKED
             self.activated[slot] = f == 1  # byte_tracker.py:130-131
             self.wasrem[slot] = False
@@ -334,7 +348,7 @@ class StreamTracker:
         a = [int(i) for i in np.flatnonzero(self.state == TRACKED)]
         b = [int(i) for i in np.flatnonzero((self.state == LOST) | (self.state == REMOVED))]
         if a and b:
-            dist = iou_cost(track_boxes(self.mean[a]), track_boxes(self.mean[b]))
+            dist = iou_cost(self._track_boxes(self.mean[a]), self._track_boxes(self.mean[b]))
             self._tell("duplicates", dist=dist, a=a, b=b)
             for p, q in zip(*np.where(dist < F32(DUPLICATE_DIST))):
                 sa, sb = a[p], b[q]
@@ -350,7 +364,7 @@ class StreamTracker:
         live.sort(key=lambda i: int(self.tid[i]))
         out = np.zeros((len(live), 8), dtype=F32)
         if live:
-            out[:, :4] = track_boxes(self.mean[live])
+            out[:, :4] = self._track_boxes(self.mean[live])
             out[:, 4] = self.tid[live].astype(F32)
             out[:, 5] = self.score[live]
             out[:, 6] = self.cls[live]
